@@ -6,7 +6,13 @@ A "step" is one pass of the hot path over one batch of candidate poses: pose bat
 background -> rot90 + CLIP preprocess -> ViT forward -> logits against the cached text
 embeddings, then (N>1) ONE all-gather of logits, ratio, smoothing, argmax.
 
-python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (value, ms_per_step and the roofline figures
+read from the timed steps' own device timers).  --full adds what takes work of its own after the timed steps: the CPU
+baseline with its parity check against the oracle (--cpu-sample), the per-product ViT event times (--product-steps)
+and the rocm-smi power line (--power-seconds).  --dump-outputs DIR writes what the last timed step computed (gathered
+logits, smoothed scores, the best pose) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
 
 Default workload (no --config): BASELINE.json configs[1] — synthetic "shopping" scene (seeded,
 SURVEY.md §8(d)), 4 096 candidate poses per GPU, 640x360 renders, ViT-B/16, bf16 MFMA with fp32
@@ -29,8 +35,8 @@ reference vision_3d/obj_pose_opt.py:16-36):
      misses the 1e-3 parity bar) and says so in the line.
 Individual flags (--scene, --sample-res, --clip, --width, --height, --scaling, ...) override the table.
 
-With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) the script re-executes itself under
-`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`.
+With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) the script runs itself as a child process under
+`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` and exits with its status.
 """
 import argparse
 import json
@@ -240,8 +246,10 @@ def cpu_baseline(scene, W, H, cfg, sd, text, poses_world, n_sample):
 
 
 def self_launch(n: int):
-    """`python bench.py --gpus N` outside a launcher: become `torch.distributed.run` with N ranks."""
+    """`python bench.py --gpus N` outside a launcher: run `torch.distributed.run` with N ranks as a fresh child process (not
+    an exec: torch.cuda.device_count() below may already have opened the GPU in this one) and exit with its status."""
     import socket
+    import subprocess
     import torch
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -260,7 +268,8 @@ def self_launch(n: int):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 # BASELINE.json configs[0..4] as named workloads (pose-grid bounds per scene type:
@@ -630,7 +639,7 @@ def run_api(args, wd):
             "peak_host_rss_gb": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1048576, 2),
             "argmax_pose": int(np.argmax(sc)),
             "roofline": None, "cpu_baseline": None,
-            "note": "API-level line (bench.py --api): the kernel-level line with roofline and cpu_baseline is the default `python bench.py`",
+            "note": "API-level line (bench.py --api): the kernel-level line with roofline is the default `python bench.py`, cpu_baseline is `python bench.py --full`",
         }
         print(json.dumps(out), flush=True)
         if not args.api_dir:
@@ -815,7 +824,7 @@ def main():
                          "defaults to 8: one GPU = a 1/8 slice; 1 = the whole grid)")
     ap.add_argument("--clip", default=None)
     ap.add_argument("--product-steps", type=int, default=2,
-                    help="extra untimed steps after the timed region with an event pair around every product of the vision tower "
+                    help="--full: extra untimed steps after the timed region with an event pair around every product of the vision tower "
                          "(roofline.products: QKV / attention / out-proj / fc1 / fc2); 0 = skip")
     ap.add_argument("--scene", default=None)
     ap.add_argument("--lens", choices=("demo", "none"), default="demo",
@@ -827,9 +836,15 @@ def main():
     ap.add_argument("--vit-fp8", action="store_true",
                     help="the ViT's Linear products on the fp8 MFMA (library option vit_fp8; configs[4] is worded \"fp8 MFMA ViT\"); NOT within "
                          "north_star's 1e-3 of the fp32 oracle, hence not the default")
-    ap.add_argument("--cpu-sample", type=int, default=32, help="candidates in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=32, help="--full: candidates in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--dump", default=None, help="rank 0: write the last step's gathered logits, scores, pose order and grid to this .npz (tests)")
-    ap.add_argument("--power-seconds", type=float, default=2.5, help="extra untimed seconds sampled with rocm-smi for the power line (0 = skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: write what the last TIMED step computed as DIR/<name>.npy (float32): logits (gathered, [poses per step, 2]), "
+                         "scores (smoothed, [poses in the grid]), best_pose (the arg-max pose, [16], world frame)")
+    ap.add_argument("--power-seconds", type=float, default=2.5, help="--full: extra untimed seconds sampled with rocm-smi for the power line (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the CPU baseline and the parity of its "
+                         "sample against the GPU's logits (--cpu-sample), roofline.products (--product-steps) and the power line (--power-seconds)")
     ap.add_argument("--api", action="store_true",
                     help="time the drop-in API (ImaginationEngine.dream_best_pose) instead of the kernel-level step; without --config: "
                          "the reference's own workload (70 000 poses, 336x336, ViT-L/14-336, physics on)")
@@ -1006,6 +1021,11 @@ def run_kernel_bench(args, wd):
         best, scores = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        # before any untimed step of --full can overwrite them: what a caller of the timed path receives from its last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("logits", step.logits), ("scores", scores), ("best_pose", pose_batch[best])):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.asarray(a, np.float32))
     wd.stage("result reduction (all_reduce) and report", 1200)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64,
@@ -1023,7 +1043,7 @@ def run_kernel_bench(args, wd):
     # per-product device time of the vision tower ("timing" 2: an event pair around every product launch) over EXTRA, untimed
     # steps after the timed region — the events cost a few tenths of a per cent of a step, so they stay out of `value`
     vit_products = None
-    if rank == 0 and world == 1 and args.product_steps > 0:
+    if rank == 0 and world == 1 and args.full and args.product_steps > 0:
         ctx.set_option("timing", 2)
         for _ in range(args.product_steps):
             step()
@@ -1156,8 +1176,8 @@ def run_kernel_bench(args, wd):
         }
         out["roofline_vit"] = out["roofline"]          # the name older readers look for: the same object
         if world == 1:
-            out["power"] = power_probe(step, dev.index or 0, args.power_seconds)
-        if world == 1 and args.cpu_sample > 0:
+            out["power"] = power_probe(step, dev.index or 0, args.power_seconds) if args.full else None
+        if world == 1 and args.full and args.cpu_sample > 0:
             cb, frames_o, lg_o, idx = cpu_baseline(scene, W, H, cfg, sd, text, pose_batch[my_idx], args.cpu_sample)
             out["cpu_baseline"] = cb
             # same candidates through the GPU path: parity of the benchmark itself

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 def run_bench(tmp_path, *flags, timeout=1500):
     dump = str(tmp_path / "dump.npz")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--power-seconds", "0", "--dump", dump, *flags],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--power-seconds", "0", "--dump", dump, *flags],
                        env=env, capture_output=True, text=True, timeout=timeout, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -8,10 +8,10 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
 line() { grep '^{"metric"' | tail -1; }
-python bench.py --config 4 --steps 2 --warmup 1 --cpu-sample 8            2>$OUT/cfg4_bf16.err | line > $OUT/${TAG}_cfg4_bf16_bench.json
-python bench.py --config 4 --steps 2 --warmup 1 --cpu-sample 8 --vit-fp8  2>$OUT/cfg4_fp8.err  | line > $OUT/${TAG}_cfg4_fp8_bench.json
-python bench.py --config 1 --steps 5 --warmup 2 --cpu-sample 32 --vit-fp8 2>$OUT/cfg1_fp8.err  | line > $OUT/${TAG}_cfg1_fp8_bench.json
-python bench.py --clip vit_l14_336 --width 336 --height 336 --poses-per-gpu 1024 --steps 3 --warmup 1 --cpu-sample 4 --vit-fp8 2>$OUT/ref_fp8.err | line > $OUT/${TAG}_refshapes_fp8_bench.json
+python bench.py --full --config 4 --steps 2 --warmup 1 --cpu-sample 8            2>$OUT/cfg4_bf16.err | line > $OUT/${TAG}_cfg4_bf16_bench.json
+python bench.py --full --config 4 --steps 2 --warmup 1 --cpu-sample 8 --vit-fp8  2>$OUT/cfg4_fp8.err  | line > $OUT/${TAG}_cfg4_fp8_bench.json
+python bench.py --full --config 1 --steps 5 --warmup 2 --cpu-sample 32 --vit-fp8 2>$OUT/cfg1_fp8.err  | line > $OUT/${TAG}_cfg1_fp8_bench.json
+python bench.py --full --clip vit_l14_336 --width 336 --height 336 --poses-per-gpu 1024 --steps 3 --warmup 1 --cpu-sample 4 --vit-fp8 2>$OUT/ref_fp8.err | line > $OUT/${TAG}_refshapes_fp8_bench.json
 for f in $OUT/${TAG}_*_bench.json; do python - $f <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

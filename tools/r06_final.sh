@@ -9,14 +9,14 @@ mkdir -p $OUT
 cd $ROOT
 line() { grep '^{"metric"' | tail -1; }
 if [ "${R06_SUITE:-1}" = "1" ]; then (timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -15) > $OUT/${TAG}_gpu_suite.txt; fi
-python bench.py --config 1 --steps 20 --warmup 5                2>$OUT/cfg1.err | line > $OUT/${TAG}_cfg1_bench.json
-python bench.py --config 1 --steps 10 --warmup 3 --cpu-sample 0 --power-seconds 0 --lens none     2>$OUT/cfg1nl.err | line > $OUT/${TAG}_cfg1_nolens_bench.json
-python bench.py --config 1 --steps 10 --warmup 3 --cpu-sample 32 --power-seconds 0 --opt mlp_f16=0 2>$OUT/cfg1bf.err | line > $OUT/${TAG}_cfg1_bf16mlp_bench.json
-python bench.py --config 0 --steps 5 --warmup 2                 2>$OUT/cfg0.err | line > $OUT/${TAG}_cfg0_bench.json
-python bench.py --config 2 --steps 3 --warmup 1 --cpu-sample 16 2>$OUT/cfg2.err | line > $OUT/${TAG}_cfg2_bench.json
-python bench.py --config 3 --steps 2 --warmup 1 --cpu-sample 16 2>$OUT/cfg3.err | line > $OUT/${TAG}_cfg3_bench.json
-python bench.py --config 4 --steps 2 --warmup 1 --cpu-sample 8  2>$OUT/cfg4.err | line > $OUT/${TAG}_cfg4_bench.json
-python bench.py --clip vit_l14_336 --width 336 --height 336 --poses-per-gpu 1024 --steps 3 --warmup 1 --cpu-sample 4 2>$OUT/ref.err | line > $OUT/${TAG}_refshapes_bench.json
+python bench.py --full --config 1 --steps 20 --warmup 5                2>$OUT/cfg1.err | line > $OUT/${TAG}_cfg1_bench.json
+python bench.py --full --config 1 --steps 10 --warmup 3 --cpu-sample 0 --power-seconds 0 --lens none     2>$OUT/cfg1nl.err | line > $OUT/${TAG}_cfg1_nolens_bench.json
+python bench.py --full --config 1 --steps 10 --warmup 3 --cpu-sample 32 --power-seconds 0 --opt mlp_f16=0 2>$OUT/cfg1bf.err | line > $OUT/${TAG}_cfg1_bf16mlp_bench.json
+python bench.py --full --config 0 --steps 5 --warmup 2                 2>$OUT/cfg0.err | line > $OUT/${TAG}_cfg0_bench.json
+python bench.py --full --config 2 --steps 3 --warmup 1 --cpu-sample 16 2>$OUT/cfg2.err | line > $OUT/${TAG}_cfg2_bench.json
+python bench.py --full --config 3 --steps 2 --warmup 1 --cpu-sample 16 2>$OUT/cfg3.err | line > $OUT/${TAG}_cfg3_bench.json
+python bench.py --full --config 4 --steps 2 --warmup 1 --cpu-sample 8  2>$OUT/cfg4.err | line > $OUT/${TAG}_cfg4_bench.json
+python bench.py --full --clip vit_l14_336 --width 336 --height 336 --poses-per-gpu 1024 --steps 3 --warmup 1 --cpu-sample 4 2>$OUT/ref.err | line > $OUT/${TAG}_refshapes_bench.json
 for f in $OUT/${TAG}_*_bench.json; do python - $f <<'PY'
 import json, sys
 try:
