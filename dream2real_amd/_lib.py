@@ -9,7 +9,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libd2r.so")
-ABI_VERSION = 9          # D2R_ABI_VERSION of include/d2r.h this binding was written against
+ABI_VERSION = 10        # D2R_ABI_VERSION of include/d2r.h this binding was written against
 
 EXPORTS = [
     "d2r_abi_version", "d2r_ctx_create", "d2r_ctx_destroy", "d2r_ctx_set_stream", "d2r_ctx_synchronize",
@@ -21,6 +21,7 @@ EXPORTS = [
     "d2r_allgather_scores", "d2r_phys_create", "d2r_phys_destroy", "d2r_phys_check", "d2r_nerf_load_ingp", "d2r_lens_undistort_view",
     "d2r_rectify_background_depth", "d2r_ingp_inspect", "d2r_render_score_host", "d2r_png_write", "d2r_png_write_batch",
     "d2r_png_read_batch", "d2r_png_size", "d2r_savetxt", "d2r_ingp_validate", "d2r_debug_gemm_fp8", "d2r_ctx_get_option", "d2r_png_write_batch_bg",
+    "d2r_pcd_create", "d2r_pcd_destroy", "d2r_pcd_render", "d2r_pcd_render_score_host",
 ]
 
 
@@ -74,6 +75,11 @@ class IngpInfo(C.Structure):
                 ("n_unknown_keys", C.c_uint32), ("render_with_lens_distortion", C.c_int32)]
 
 
+class PcdView(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("point_size", C.c_float), ("near", C.c_float)]
+
+
 class FrameSink(C.Structure):
     _fields_ = [("png_dir", C.c_char_p), ("png_first_index", C.c_uint32), ("png_threads", C.c_int32), ("png_level", C.c_int32)]
 
@@ -121,6 +127,7 @@ def load() -> C.CDLL:
     lib.d2r_clip_destroy.restype = None
     lib.d2r_text_destroy.restype = None
     lib.d2r_phys_destroy.restype = None
+    lib.d2r_pcd_destroy.restype = None
     for name in EXPORTS:
         getattr(lib, name)          # every declared symbol must be exported
     if lib.d2r_abi_version() != ABI_VERSION:

@@ -168,8 +168,24 @@ def optimise_pose_grid(renderer, depths_gt, render_cam_pose_idx, task_model, dat
         if physics_only:
             best = int(torch.randint(valid_idxs.shape[0], (1,)).item())
             return torch.from_numpy(valid_poses[best].reshape(4, 4).copy()), torch.from_numpy(pose_batch), torch.ones(N)
-        if use_vis_pcds:
-            raise NotImplementedError("the point-cloud ablation renderer is outside the path")
+    if not use_cache_renders and use_vis_pcds:
+        # reference :129-131: view 0 only, its OpenCV pose unconverted, the world-frame candidate poses; no cb_render files
+        if not getattr(renderer, "point_cloud", False):
+            raise NotImplementedError("use_vis_pcds=True needs a pcd_visual_model.PointCloudRenderer (or a renderer with "
+                                      "its render(render_pose, pose_batch, task_model) surface and point_cloud = True)")
+        if shard is not None or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise NotImplementedError("pose sharding of the point-cloud ablation (use_vis_pcds) is not implemented")
+        render_poses = get_virtual_cam_poses(task_model, render_cam_pose_idx)
+        te, n_goal = text_embeddings()
+        lap("convert_poses_and_text")
+        if hasattr(renderer, "render_score") and hasattr(scorer, "h"):
+            all_logits = renderer.render_score(render_poses[0], valid_poses, task_model, scorer, te)
+        else:
+            all_logits = scorer.score_frames(np.stack(renderer.render(render_poses[0], valid_poses, task_model)), te,
+                                             rot90=True)
+        lap("render_score")
+        fetch_render = lambda j: renderer.render(render_poses[0], valid_poses[j:j + 1], task_model)[0]
+    elif not use_cache_renders:
         render_poses = get_virtual_cam_poses(task_model, render_cam_pose_idx)
         render_poses_ngp = accio2ngp.converter(render_poses)
         valid_poses_ngp = accio2ngp.converter(valid_poses.reshape(-1, 4, 4))

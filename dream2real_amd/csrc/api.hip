@@ -160,7 +160,8 @@ void d2r_ctx_destroy(d2r_ctx *c)
     delete c->pool;
     d2r_ctx::Buf *bufs[] = {&c->cams, &c->queue, &c->queue2, &c->sort_counts, &c->counters, &c->frames, &c->rgba, &c->depth, &c->poses,
                             &c->text, &c->logits, &c->pix, &c->bg_rgba, &c->bg_depth, &c->bg_u8, &c->rects, &c->bg_patches, &c->rect_ws, &c->lens_tab,
-                            &c->patches2, &c->frames2, &c->bg_l0, &c->l0_a1, &c->l0_q2, &c->l0_misc};
+                            &c->patches2, &c->frames2, &c->bg_l0, &c->l0_a1, &c->l0_q2, &c->l0_misc,
+                            &c->pcd_mats, &c->pcd_bg_keys, &c->pcd_bg_frame, &c->pcd_cols};
     for (auto *b : bufs)
         if (b->p) hipFree(b->p);
     for (auto &b : c->clipws)

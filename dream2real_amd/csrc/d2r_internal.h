@@ -125,6 +125,7 @@ struct d2r_ctx {
     uint32_t text_turn = 0;
     // background of the current view
     Buf bg_rgba, bg_depth, bg_u8;
+    Buf pcd_mats, pcd_bg_keys, pcd_bg_frame, pcd_cols;   // pcd.hip: candidate matrices, background key buffer and colour frame, colour table of the current call
     Buf lens_tab;                // undistorted camera-space directions of the current view's pixels (nerf.hip lens_table)
     float lens_key[10] = {};     // ... and the view (size, intrinsics, coefficients) it was computed for
     bool lens_key_valid = false;

@@ -53,8 +53,6 @@ class ImaginationEngine:
     """The slice of the reference's ImaginationEngine around dream_best_pose."""
 
     def __init__(self, cfg: PathConfig, ctx, scorer, *, text_embeds=None, text_encoder=None, tokenizer=None, depths_gt=None):
-        if cfg.use_vis_pcds:
-            raise NotImplementedError("the point-cloud ablation renderer is outside the path")
         self.cfg, self.ctx, self.scorer = cfg, ctx, scorer
         self.text_embeds, self.text_encoder, self.tokenizer = text_embeds, text_encoder, tokenizer
         self.depths_gt = depths_gt                       # [L, h, w] sensor depth of the render views (dream2real.py:117-118), or None
@@ -82,7 +80,11 @@ class ImaginationEngine:
         else:                                                                                    # :324-326
             phys_check = lambda pose_batch, task_model, valid_so_far: torch.ones(len(pose_batch), dtype=torch.bool)
 
-        self.renderer = combined_rendering.renderer(self.data_dir, task_model, resolution=cfg.resolution)   # :332
+        if cfg.use_vis_pcds and not cfg.use_cache_goal_pose:                                     # :329-332
+            from .pcd_visual_model import PointCloudRenderer
+            self.renderer = PointCloudRenderer(self.ctx)
+        else:
+            self.renderer = combined_rendering.renderer(self.data_dir, task_model, resolution=cfg.resolution)
 
         if cfg.use_cache_goal_pose:                                                              # :335-341
             best_pose = torch.tensor(np.loadtxt(os.path.join(self.data_dir, "goal_pose.txt"))).float()

@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 #define D2R_API __attribute__((visibility("default")))
-#define D2R_ABI_VERSION 9
+#define D2R_ABI_VERSION 10
 
 typedef enum {
     D2R_OK = 0,
@@ -579,6 +579,55 @@ typedef struct {
  */
 D2R_API int d2r_phys_check(d2r_ctx *ctx, const d2r_phys *phys, const d2r_phys_params *params, const float *pose_batch,
                            uint32_t N, uint8_t *valid_io);
+
+/* ------------------------------------------------- point-cloud ablation renderer (use_vis_pcds)
+ *
+ * replaces reference vision_3d/pcd_visual_model.py:98-155 (PointCloudRenderer.render: Open3D / Filament, one frame per
+ * candidate, serially) behind clip_scoring.py:129-131.  The render rule is pinned in DESIGN.md section 2 instead of
+ * Filament's rasteriser: pinhole projection u = fx x / z + cx, v = fy y / z + cy (pixel (row i, col j) centred at
+ * (u, v) = (j, i)); points with z <= near are culled; a point covers the point_size x point_size pixels from
+ * (ceil(u - point_size / 2), ceil(v - point_size / 2)); the nearest point wins, ties to the lower global index (background
+ * points in cloud order, then movable points); its 8-bit colour is written unchanged, white where no point lands; then any
+ * pixel whose three channels are all > 220 becomes (0, 0, 0) (reference :145-147).
+ */
+typedef struct d2r_pcd d2r_pcd;
+
+/* A coloured point cloud on the context's device: xyz host [n][3] fp32, rgb host [n][3] uint8 (n may be 0). */
+D2R_API int d2r_pcd_create(d2r_ctx *ctx, const float *xyz, const uint8_t *rgb, uint32_t n, d2r_pcd **out);
+D2R_API void d2r_pcd_destroy(d2r_pcd *pcd);
+
+typedef struct {
+    uint32_t width, height;     /* 336 x 336 in the reference */
+    float fx, fy, cx, cy;       /* INTRINSICS_CLIP_VIEW: 436.01158022, 435.90814372, 168, 168 */
+    float point_size;           /* sprite side in pixels: a whole number 1 .. 16 (the reference's MaterialRecord: 3) */
+    float near;                 /* points with camera-space z <= near are culled (believed value 0.01 m) */
+} d2r_pcd_view;
+
+/*
+ * Parity hook: K frames to the host.
+ *   cam_pose      host [16] fp32, row-major camera-to-world pose in the OpenCV convention (get_virtual_cam_poses(...)[0],
+ *                 NOT passed through accio2ngp.converter); the camera's extrinsic is its rigid inverse
+ *   obj_pose_now  host [16] the movable object's current pose O
+ *   obj_poses     host [K][16] candidate poses P_k; the movable cloud moves by P_k inv(O), the background does not move
+ *   frames_out    host [K][h][w][3] uint8
+ * Per candidate the 3x4 matrix inv(cam_pose) P_k inv(O) is composed in fp64 (rigid inverses [R^T | -R^T t], each entry
+ * summed over l = 0..3 in order), rounded to fp32; points then take fp32 multiply-adds ((m0 x + m1 y) + m2 z) + m3 per
+ * row and a correctly rounded fp32 divide.  Synchronous.
+ */
+D2R_API int d2r_pcd_render(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *movable, const d2r_pcd_view *view,
+                           const float *cam_pose, const float *obj_pose_now, const float *obj_poses, uint32_t K,
+                           uint8_t *frames_out);
+
+/*
+ * The fused pass of the ablation (reference clip_scoring.py:129-185): render the K candidates on the GPU and score them
+ * (rot90 + CLIPProcessor + vision tower + logits_per_image), in the chunks d2r_clip_score_frames uses; the frames never
+ * leave the device unless frames_out (host [K][h][w][3] uint8) is given.  Logits equal d2r_clip_score_frames(frames,
+ * rot90 = 1) of the same frames.  Synchronous.
+ */
+D2R_API int d2r_pcd_render_score_host(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *movable, const d2r_clip *clip,
+                                      const d2r_pcd_view *view, const float *cam_pose, const float *obj_pose_now,
+                                      const float *obj_poses, uint32_t K, const float *text_embeds, uint32_t C,
+                                      float logit_scale, float *logits_out, uint8_t *frames_out);
 
 #ifdef __cplusplus
 }
