@@ -28,7 +28,7 @@ uint32_t d2r_clip_tokens(const d2r_clip *);
 
 // Candidates (images) per pass: the "chunk" option, capped so that one pass stays inside the 32-bit
 // indexing of the ray queue (rays) and of the GEMM outputs (rows x widest layer).
-static uint32_t pass_size(const d2r_ctx *ctx, const d2r_clip *clip, size_t px)
+uint32_t d2r_pass_size(const d2r_ctx *ctx, const d2r_clip *clip, size_t px)
 {
     uint64_t per = (uint64_t)std::max<int64_t>(1, ctx->chunk);
     if (clip) per = std::min<uint64_t>(per, d2r_clip_max_images(clip));
@@ -62,6 +62,154 @@ int d2r_reserve(d2r_ctx *ctx, d2r_ctx::Buf &b, size_t bytes)
     b.cap = want - 64;     // kernels may read a few bytes past the last element (k_preprocess: 4-byte pixel loads)
     D2R_HIP(ctx, hipMemsetAsync(b.p, 0, want, ctx->stream));   // padded rows/columns of GEMM operands must be finite
     return D2R_OK;
+}
+
+// Candidates per pass when frames leave the GPU: at most 1 GiB of frames (render_score_body: per pinned staging buffer;
+// d2r_pcd_render: on the device), but no fewer than 64.
+uint32_t d2r_frame_pass_size(uint32_t per, size_t px)
+{
+    const uint64_t fit = std::max<uint64_t>(64, (1ull << 30) / (px * 3));
+    uint64_t p = std::min<uint64_t>(per, fit);
+    if (p >= 256) p -= p % 256;
+    return (uint32_t)std::max<uint64_t>(1, p);
+}
+
+int d2r_upload_text(d2r_ctx *ctx, const d2r_clip *clip, const float *text, uint32_t C)
+{
+    if (!text || C == 0 || C > 1024) return d2r_fail(ctx, D2R_ERR_INVALID, "bad text embeddings");
+    size_t bytes = (size_t)C * d2r_clip_proj_dim(clip) * 4;
+    int rc = d2r_reserve(ctx, ctx->text, bytes);
+    if (rc) return rc;
+    // staged through a pinned slot: the caller's buffer is fully read before this returns (d2r.h: "host pointers are
+    // read before the call returns"), and the copy itself stays asynchronous on the context's stream
+    const uint32_t slot = ctx->text_turn++ & 1u;
+    if (ctx->text_ev[slot]) D2R_HIP(ctx, hipEventSynchronize(ctx->text_ev[slot]));        // the slot's previous copy has left it
+    else D2R_HIP(ctx, hipEventCreateWithFlags(&ctx->text_ev[slot], hipEventDisableTiming));
+    if (ctx->text_host_cap[slot] < bytes) {
+        if (ctx->text_host[slot]) (void)hipHostFree(ctx->text_host[slot]);
+        ctx->text_host[slot] = nullptr;
+        ctx->text_host_cap[slot] = 0;
+        if (hipHostMalloc(&ctx->text_host[slot], bytes + 4096, hipHostMallocDefault) != hipSuccess)
+            return d2r_fail(ctx, D2R_ERR_MEMORY, "hipHostMalloc failed for the text staging buffer");
+        ctx->text_host_cap[slot] = bytes + 4096;
+    }
+    memcpy(ctx->text_host[slot], text, bytes);
+    D2R_HIP(ctx, hipMemcpyAsync(ctx->text.p, ctx->text_host[slot], bytes, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipEventRecord(ctx->text_ev[slot], ctx->stream));
+    return D2R_OK;
+}
+
+// The scoring loop of the entry points whose frames do not come out of the NeRF pipeline (render_score_body keeps its own: two
+// streams, the pinned frame ring, layer-0 reuse).  For each pass [c0, c0 + nc) fill(c0, nc) leaves nc frames [nc][h][w][3] in
+// ctx->frames on ctx->stream; then rot90 + CLIP preprocess, the vision tower, and the pass's logits (embeddings, frames) to the
+// host.  The text embeddings are on the device already (d2r_upload_text).  The workspaces are sized once for a full pass, so
+// that no allocation happens inside the loop.
+int d2r_score_frames_chunked(d2r_ctx *ctx, const d2r_clip *clip, uint32_t n, uint32_t w, uint32_t h, int rot90, uint32_t C,
+                             float logit_scale, const std::function<int(uint32_t, uint32_t)> &fill, float *logits_out,
+                             float *embeds_out, uint8_t *frames_out)
+{
+    if (n == 0) return D2R_OK;
+    const size_t fb = (size_t)w * h * 3;
+    const uint32_t D = d2r_clip_proj_dim(clip);
+    const uint32_t per = d2r_pass_size(ctx, clip, 0), cap = std::min(per, n);
+    int rc;
+    if ((rc = d2r_reserve(ctx, ctx->frames, (size_t)cap * fb))) return rc;
+    if ((rc = d2r_reserve(ctx, ctx->clipws[6], d2r_clip_patch_bytes(clip, cap)))) return rc;
+    if ((rc = d2r_reserve(ctx, ctx->logits, (size_t)cap * (C + D) * 4))) return rc;
+    for (uint32_t c0 = 0; c0 < n; c0 += per) {
+        const uint32_t nc = std::min(per, n - c0);
+        float *lg = (float *)ctx->logits.p, *em = lg + (size_t)nc * C;
+        if ((rc = fill(c0, nc))) return rc;
+        if ((rc = d2r_launch_preprocess(ctx, (d2r_clip *)clip, (const uint8_t *)ctx->frames.p, nc, w, h, rot90,
+                                        (uint16_t *)ctx->clipws[6].p, nullptr)))
+            return rc;
+        if ((rc = d2r_clip_forward(ctx, clip, (const uint16_t *)ctx->clipws[6].p, nc, (const float *)ctx->text.p, C,
+                                   logit_scale, lg, em)))
+            return rc;
+        D2R_HIP(ctx, hipMemcpyAsync(logits_out + (size_t)c0 * C, lg, (size_t)nc * C * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (embeds_out)
+            D2R_HIP(ctx, hipMemcpyAsync(embeds_out + (size_t)c0 * D, em, (size_t)nc * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (frames_out)
+            D2R_HIP(ctx, hipMemcpyAsync(frames_out + (size_t)c0 * fb, ctx->frames.p, (size_t)nc * fb, hipMemcpyDeviceToHost, ctx->stream));
+        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return D2R_OK;
+}
+
+// ---------------------------------------------------------------- options
+// Every key of d2r_ctx_set_option / d2r_ctx_get_option (include/d2r.h lists them for callers).  The defaults, and why each is
+// what it is, stand beside the members in struct d2r_ctx.
+struct Option {
+    const char *key;
+    int64_t d2r_ctx::*member;
+    enum Kind { FLAG, RANGE, FREE } kind;   // FLAG: stored as value != 0; RANGE: lo <= value <= hi or D2R_ERR_INVALID; FREE: any value
+    int64_t lo, hi;
+    unsigned flags;
+    int (*hook)(d2r_ctx *, int64_t value);  // optional, after the range check and before the store: a further check or a side effect
+};
+enum { OPT_DEV = 1,          // experiment switch of development builds (make DEV=1): schedules that were measured no faster and tile
+                             // configurations kept for comparison; a product build does not know the key
+       OPT_READ_ONLY = 2 };  // read-back of what the last launch ran with
+#ifdef D2R_DEV
+static const bool kDevBuild = true;
+#else
+static const bool kDevBuild = false;
+#endif
+
+static int opt_march_threads(d2r_ctx *ctx, int64_t value)
+{
+    if (value % 64)
+        return d2r_fail(ctx, D2R_ERR_INVALID, "march_threads must be 0 (auto) or a multiple of 64 up to " + std::to_string(D2R_MARCH_THREADS) + " (the size the marcher was compiled for)");
+    return D2R_OK;
+}
+
+static int opt_timing(d2r_ctx *ctx, int64_t)
+{
+    ctx->ev_used = 0;
+    ctx->ev_pairs.clear();
+    return D2R_OK;
+}
+
+static const Option g_options[] = {
+    {"chunk", &d2r_ctx::chunk, Option::RANGE, 1, 16384},
+    {"march_compact", &d2r_ctx::march_compact, Option::RANGE, 0, 1},
+    {"refill_min", &d2r_ctx::refill_min, Option::RANGE, 1, 64},
+    {"ln_fold", &d2r_ctx::ln_fold, Option::RANGE, 0, 4},
+    {"gemm_nsplit", &d2r_ctx::gemm_nsplit, Option::FREE},
+    {"prep_reuse", &d2r_ctx::prep_reuse, Option::FLAG},
+    {"cls_last", &d2r_ctx::cls_last, Option::FLAG},
+    {"vit_fp8", &d2r_ctx::vit_fp8, Option::FLAG},
+    {"l0_reuse", &d2r_ctx::l0_reuse, Option::FLAG},
+    {"attn_rem", &d2r_ctx::attn_rem, Option::RANGE, 0, 4},
+    {"overlap", &d2r_ctx::overlap, Option::FLAG},
+    {"debug_fail_chunk", &d2r_ctx::debug_fail_chunk, Option::FREE},     // test hook, ONE-SHOT: the next d2r_render_score* fails in this chunk, then the hook disarms itself (-1 = off)
+    {"ray_sort", &d2r_ctx::ray_sort, Option::RANGE, 0, 1},
+    {"ray_sort_log2", &d2r_ctx::ray_sort_log2, Option::RANGE, 1, 4},
+    {"march_threads", &d2r_ctx::march_threads, Option::RANGE, 0, D2R_MARCH_THREADS, 0, opt_march_threads},
+    {"march_threads_auto_mib", &d2r_ctx::march_threads_auto_mib, Option::RANGE, 0, 1 << 20},
+    {"march_blocks", &d2r_ctx::march_blocks, Option::RANGE, 0, 65535},
+    {"gemm_cfg", &d2r_ctx::gemm_cfg, Option::FREE, 0, 0, OPT_DEV},
+    {"gemm_group", &d2r_ctx::gemm_group, Option::RANGE, 0, 65535, OPT_DEV},
+    {"gemm_stagger", &d2r_ctx::gemm_stagger, Option::FLAG, 0, 0, OPT_DEV},
+    {"gbrick_slots", &d2r_ctx::gbrick_slots, Option::RANGE, 0, 8},
+    {"brick_slots_total", &d2r_ctx::brick_slots_total, Option::RANGE, 0, 8},
+    {"lds_slots_max", &d2r_ctx::lds_slots_max, Option::RANGE, 0, 5},      // read by d2r_nerf_create: set it before creating the model
+    {"gbrick_max_mib", &d2r_ctx::gbrick_max_mib, Option::RANGE, 0, 512},  // read by d2r_nerf_create too
+    {"mlp_f16", &d2r_ctx::mlp_f16, Option::FLAG},
+    {"bricks", &d2r_ctx::use_bricks, Option::FLAG},
+    {"raygen_rect", &d2r_ctx::raygen_rect, Option::FLAG},
+    {"timing", &d2r_ctx::timing, Option::RANGE, 0, 2, 0, opt_timing},
+    {"march_lds_slots", &d2r_ctx::last_march_nb, Option::FREE, 0, 0, OPT_READ_ONLY},
+    {"march_hbm_brick_slots", &d2r_ctx::last_march_ngb, Option::FREE, 0, 0, OPT_READ_ONLY},
+    {"march_hbm_brick_bytes", &d2r_ctx::last_march_gbrick_bytes, Option::FREE, 0, 0, OPT_READ_ONLY},
+    {"march_threads_used", &d2r_ctx::last_march_threads, Option::FREE, 0, 0, OPT_READ_ONLY},
+};
+
+static const Option *find_option(const char *key)
+{
+    for (const Option &o : g_options)
+        if (!strcmp(key, o.key)) return (o.flags & OPT_DEV) && !kDevBuild ? nullptr : &o;
+    return nullptr;
 }
 
 size_t d2r_ctx::timing_begin(int kind)
@@ -201,108 +349,24 @@ int d2r_ctx_synchronize(d2r_ctx *ctx)
 int d2r_ctx_set_option(d2r_ctx *ctx, const char *key, int64_t value)
 {
     if (!ctx || !key) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
-    if (!strcmp(key, "chunk")) {
-        if (value < 1 || value > 16384) return d2r_fail(ctx, D2R_ERR_INVALID, "chunk must be in [1, 16384]");
-        ctx->chunk = value;
-    } else if (!strcmp(key, "march_compact")) {
-        if (value < 0 || value > 1) return d2r_fail(ctx, D2R_ERR_INVALID, "march_compact must be 0 or 1");
-        ctx->march_compact = value;
-    } else if (!strcmp(key, "refill_min")) {
-        if (value < 1 || value > 64) return d2r_fail(ctx, D2R_ERR_INVALID, "refill_min must be in [1, 64]");
-        ctx->refill_min = value;
-    } else if (!strcmp(key, "ln_fold")) {
-        if (value < 0 || value > 4) return d2r_fail(ctx, D2R_ERR_INVALID, "ln_fold must be 0..4");
-        ctx->ln_fold = value;
-    } else if (!strcmp(key, "gemm_nsplit")) {
-        ctx->gemm_nsplit = value;
-    } else if (!strcmp(key, "prep_reuse")) {
-        ctx->prep_reuse = value != 0;
-    } else if (!strcmp(key, "cls_last")) {
-        ctx->cls_last = value != 0;
-    } else if (!strcmp(key, "vit_fp8")) {
-        ctx->vit_fp8 = value != 0;
-    } else if (!strcmp(key, "l0_reuse")) {
-        ctx->l0_reuse = value != 0;
-    } else if (!strcmp(key, "attn_rem")) {
-        if (value < 0 || value > 4) return d2r_fail(ctx, D2R_ERR_INVALID, "attn_rem must be 0..4");
-        ctx->attn_rem = value;
-    } else if (!strcmp(key, "overlap")) {
-        ctx->overlap = value != 0;
-    } else if (!strcmp(key, "debug_fail_chunk")) {
-        ctx->debug_fail_chunk = value;          // test hook, ONE-SHOT: the next d2r_render_score* fails in this chunk, then the hook disarms itself (-1 = off)
-    } else if (!strcmp(key, "ray_sort")) {
-        if (value < 0 || value > 1) return d2r_fail(ctx, D2R_ERR_INVALID, "ray_sort must be 0 or 1");
-        ctx->ray_sort = value;
-    } else if (!strcmp(key, "ray_sort_log2")) {
-        if (value < 1 || value > 4) return d2r_fail(ctx, D2R_ERR_INVALID, "ray_sort_log2 must be 1 .. 4");
-        ctx->ray_sort_log2 = value;
-    } else if (!strcmp(key, "march_threads")) {
-        if (value < 0 || value > D2R_MARCH_THREADS || value % 64)
-            return d2r_fail(ctx, D2R_ERR_INVALID, "march_threads must be 0 (auto) or a multiple of 64 up to " + std::to_string(D2R_MARCH_THREADS) + " (the size the marcher was compiled for)");
-        ctx->march_threads = value;
-    } else if (!strcmp(key, "march_threads_auto_mib")) {
-        if (value < 0 || value > 1 << 20) return d2r_fail(ctx, D2R_ERR_INVALID, "march_threads_auto_mib out of range");
-        ctx->march_threads_auto_mib = value;
-    } else if (!strcmp(key, "march_blocks")) {
-        if (value < 0 || value > 65535) return d2r_fail(ctx, D2R_ERR_INVALID, "march_blocks out of range");
-        ctx->march_blocks = value;
-#ifdef D2R_DEV
-    // experiment switches of development builds (make DEV=1): schedules that were measured no faster and tile
-    // configurations kept for comparison; a product build does not know these keys
-    } else if (!strcmp(key, "gemm_cfg")) {
-        ctx->gemm_cfg = value;
-    } else if (!strcmp(key, "gemm_group")) {
-        if (value < 0 || value > 65535) return d2r_fail(ctx, D2R_ERR_INVALID, "gemm_group out of range");
-        ctx->gemm_group = value;
-    } else if (!strcmp(key, "gemm_stagger")) {
-        ctx->gemm_stagger = value != 0;
-#endif
-    } else if (!strcmp(key, "gbrick_slots")) {
-        if (value < 0 || value > 8) return d2r_fail(ctx, D2R_ERR_INVALID, "gbrick_slots must be in [0, 8]");
-        ctx->gbrick_slots = value;
-    } else if (!strcmp(key, "brick_slots_total")) {
-        if (value < 0 || value > 8) return d2r_fail(ctx, D2R_ERR_INVALID, "brick_slots_total must be in [0, 8]");
-        ctx->brick_slots_total = value;
-    } else if (!strcmp(key, "lds_slots_max")) {          // read by d2r_nerf_create: set it before creating the model
-        if (value < 0 || value > 5) return d2r_fail(ctx, D2R_ERR_INVALID, "lds_slots_max must be in [0, 5]");
-        ctx->lds_slots_max = value;
-    } else if (!strcmp(key, "gbrick_max_mib")) {         // read by d2r_nerf_create too
-        if (value < 0 || value > 512) return d2r_fail(ctx, D2R_ERR_INVALID, "gbrick_max_mib must be in [0, 512]");
-        ctx->gbrick_max_mib = value;
-    } else if (!strcmp(key, "mlp_f16")) {
-        ctx->mlp_f16 = value != 0;
-    } else if (!strcmp(key, "bricks")) {
-        ctx->use_bricks = value != 0;
-    } else if (!strcmp(key, "raygen_rect")) {
-        ctx->raygen_rect = value != 0;
-    } else if (!strcmp(key, "timing")) {
-        if (value < 0 || value > 2) return d2r_fail(ctx, D2R_ERR_INVALID, "timing must be 0, 1 or 2");
-        ctx->timing = value;
-        ctx->ev_used = 0;
-        ctx->ev_pairs.clear();
-    } else {
-        return d2r_fail(ctx, D2R_ERR_INVALID, std::string("unknown option ") + key);
-    }
+    const Option *o = find_option(key);
+    if (!o) return d2r_fail(ctx, D2R_ERR_INVALID, std::string("unknown option ") + key);
+    if (o->flags & OPT_READ_ONLY) return d2r_fail(ctx, D2R_ERR_INVALID, std::string("option ") + key + " is a read-back and cannot be set");
+    if (o->kind == Option::RANGE && (value < o->lo || value > o->hi))
+        return d2r_fail(ctx, D2R_ERR_INVALID, std::string(key) + " must be in [" + std::to_string(o->lo) + ", " + std::to_string(o->hi) + "]");
+    int rc;
+    if (o->hook && (rc = o->hook(ctx, value))) return rc;
+    ctx->*(o->member) = o->kind == Option::FLAG ? (int64_t)(value != 0) : value;
     return D2R_OK;
 }
 
 int d2r_ctx_get_option(d2r_ctx *ctx, const char *key, int64_t *value)
 {
     if (!ctx || !key || !value) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
-    const struct { const char *k; int64_t v; } tab[] = {
-        {"chunk", ctx->chunk}, {"refill_min", ctx->refill_min}, {"march_compact", ctx->march_compact}, {"ln_fold", ctx->ln_fold}, {"gemm_nsplit", ctx->gemm_nsplit},
-        {"prep_reuse", ctx->prep_reuse}, {"cls_last", ctx->cls_last}, {"vit_fp8", ctx->vit_fp8}, {"l0_reuse", ctx->l0_reuse},
-        {"attn_rem", ctx->attn_rem}, {"overlap", ctx->overlap}, {"march_blocks", ctx->march_blocks}, {"march_threads", ctx->march_threads}, {"ray_sort", ctx->ray_sort}, {"ray_sort_log2", ctx->ray_sort_log2}, {"march_threads_auto_mib", ctx->march_threads_auto_mib}, {"gbrick_slots", ctx->gbrick_slots},
-        {"brick_slots_total", ctx->brick_slots_total}, {"lds_slots_max", ctx->lds_slots_max}, {"gbrick_max_mib", ctx->gbrick_max_mib},
-        {"bricks", ctx->use_bricks}, {"mlp_f16", ctx->mlp_f16}, {"raygen_rect", ctx->raygen_rect}, {"timing", ctx->timing}, {"debug_fail_chunk", ctx->debug_fail_chunk},
-        {"march_lds_slots", (int64_t)ctx->last_march_nb}, {"march_hbm_brick_slots", (int64_t)ctx->last_march_ngb},
-        {"march_hbm_brick_bytes", (int64_t)ctx->last_march_gbrick_bytes}, {"march_threads_used", (int64_t)ctx->last_march_threads}};
-    for (const auto &e : tab)
-        if (!strcmp(key, e.k)) {
-            *value = e.v;
-            return D2R_OK;
-        }
-    return d2r_fail(ctx, D2R_ERR_INVALID, std::string("unknown option ") + key);
+    const Option *o = find_option(key);
+    if (!o) return d2r_fail(ctx, D2R_ERR_INVALID, std::string("unknown option ") + key);
+    *value = ctx->*(o->member);
+    return D2R_OK;
 }
 
 int d2r_get_render_stats(d2r_ctx *ctx, d2r_render_stats *out)
@@ -664,7 +728,8 @@ int d2r_render(d2r_ctx *ctx, const d2r_nerf *model, const d2r_view *view, const 
     if (rc) return rc;
     if (n == 0) return D2R_OK;
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    const ViewParams V = d2r_view_params(view);
+    ViewParams V = d2r_view_params(view);
+    if ((rc = d2r_lens_table(ctx, V))) return rc;
     const size_t px = (size_t)V.W * V.H;
     ctx->stats = d2r_render_stats{};
     ctx->last_chunks = 0;
@@ -753,11 +818,12 @@ int d2r_render_composite(d2r_ctx *ctx, const d2r_nerf *fg, const d2r_view *view,
     int rc = check_view(ctx, view);
     if (rc) return rc;
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    const ViewParams V = d2r_view_params(view);
+    ViewParams V = d2r_view_params(view);
+    if ((rc = d2r_lens_table(ctx, V))) return rc;
     const size_t px = (size_t)V.W * V.H;
     ctx->stats = d2r_render_stats{};
     ctx->last_chunks = 0;
-    const uint32_t per = pass_size(ctx, nullptr, px);
+    const uint32_t per = d2r_pass_size(ctx, nullptr, px);
     for (uint32_t c0 = 0; c0 < K; c0 += per) {
         uint32_t nc = std::min(per, K - c0);
         if ((rc = d2r_reserve(ctx, ctx->poses, (size_t)nc * 64))) return rc;
@@ -776,61 +842,20 @@ int d2r_render_composite(d2r_ctx *ctx, const d2r_nerf *fg, const d2r_view *view,
 
 // -------------------------------------------------------------------- CLIP
 
-static int upload_text(d2r_ctx *ctx, const d2r_clip *clip, const float *text, uint32_t C)
-{
-    if (!text || C == 0 || C > 1024) return d2r_fail(ctx, D2R_ERR_INVALID, "bad text embeddings");
-    size_t bytes = (size_t)C * d2r_clip_proj_dim(clip) * 4;
-    int rc = d2r_reserve(ctx, ctx->text, bytes);
-    if (rc) return rc;
-    // staged through a pinned slot: the caller's buffer is fully read before this returns (d2r.h: "host pointers are
-    // read before the call returns"), and the copy itself stays asynchronous on the context's stream
-    const uint32_t slot = ctx->text_turn++ & 1u;
-    if (ctx->text_ev[slot]) D2R_HIP(ctx, hipEventSynchronize(ctx->text_ev[slot]));        // the slot's previous copy has left it
-    else D2R_HIP(ctx, hipEventCreateWithFlags(&ctx->text_ev[slot], hipEventDisableTiming));
-    if (ctx->text_host_cap[slot] < bytes) {
-        if (ctx->text_host[slot]) (void)hipHostFree(ctx->text_host[slot]);
-        ctx->text_host[slot] = nullptr;
-        ctx->text_host_cap[slot] = 0;
-        if (hipHostMalloc(&ctx->text_host[slot], bytes + 4096, hipHostMallocDefault) != hipSuccess)
-            return d2r_fail(ctx, D2R_ERR_MEMORY, "hipHostMalloc failed for the text staging buffer");
-        ctx->text_host_cap[slot] = bytes + 4096;
-    }
-    memcpy(ctx->text_host[slot], text, bytes);
-    D2R_HIP(ctx, hipMemcpyAsync(ctx->text.p, ctx->text_host[slot], bytes, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->text_ev[slot], ctx->stream));
-    return D2R_OK;
-}
-
 int d2r_clip_score_frames(d2r_ctx *ctx, const d2r_clip *clip, const uint8_t *frames, uint32_t n, uint32_t w,
                           uint32_t h, int rot90, const float *text_embeds, uint32_t C, float logit_scale,
                           float *logits_out, float *embeds_out)
 {
     if (!ctx || !clip || !frames || !logits_out) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = upload_text(ctx, clip, text_embeds, C);
+    int rc = d2r_upload_text(ctx, clip, text_embeds, C);
     if (rc) return rc;
-    const size_t px = (size_t)w * h;
-    const uint32_t D = d2r_clip_proj_dim(clip);
-    const uint32_t per = pass_size(ctx, clip, 0);
-    for (uint32_t c0 = 0; c0 < n; c0 += per) {
-        uint32_t nc = std::min(per, n - c0);
-        if ((rc = d2r_reserve(ctx, ctx->frames, (size_t)nc * px * 3))) return rc;
-        if ((rc = d2r_reserve(ctx, ctx->clipws[6], d2r_clip_patch_bytes(clip, nc)))) return rc;
-        if ((rc = d2r_reserve(ctx, ctx->logits, (size_t)nc * (C + D) * 4))) return rc;
-        float *lg = (float *)ctx->logits.p, *em = lg + (size_t)nc * C;
-        D2R_HIP(ctx, hipMemcpyAsync(ctx->frames.p, frames + (size_t)c0 * px * 3, (size_t)nc * px * 3, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = d2r_launch_preprocess(ctx, (d2r_clip *)clip, (const uint8_t *)ctx->frames.p, nc, w, h, rot90,
-                                        (uint16_t *)ctx->clipws[6].p, nullptr)))
-            return rc;
-        if ((rc = d2r_clip_forward(ctx, clip, (const uint16_t *)ctx->clipws[6].p, nc, (const float *)ctx->text.p, C,
-                                   logit_scale, lg, em)))
-            return rc;
-        D2R_HIP(ctx, hipMemcpyAsync(logits_out + (size_t)c0 * C, lg, (size_t)nc * C * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (embeds_out)
-            D2R_HIP(ctx, hipMemcpyAsync(embeds_out + (size_t)c0 * D, em, (size_t)nc * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return D2R_OK;
+    const size_t fb = (size_t)w * h * 3;
+    auto fill = [&](uint32_t c0, uint32_t nc) {
+        D2R_HIP(ctx, hipMemcpyAsync(ctx->frames.p, frames + (size_t)c0 * fb, (size_t)nc * fb, hipMemcpyHostToDevice, ctx->stream));
+        return (int)D2R_OK;
+    };
+    return d2r_score_frames_chunked(ctx, clip, n, w, h, rot90, C, logit_scale, fill, logits_out, embeds_out, nullptr);
 }
 
 int d2r_clip_preprocess(d2r_ctx *ctx, const d2r_clip *clip, const uint8_t *frames, uint32_t n, uint32_t w,
@@ -859,7 +884,7 @@ int d2r_clip_embed_pixels(d2r_ctx *ctx, const d2r_clip *clip, const float *pixel
     const size_t S = d2r_clip_image_size(clip);
     const uint32_t D = d2r_clip_proj_dim(clip);
     int rc;
-    const uint32_t per = pass_size(ctx, clip, 0);
+    const uint32_t per = d2r_pass_size(ctx, clip, 0);
     for (uint32_t c0 = 0; c0 < n; c0 += per) {
         uint32_t nc = std::min(per, n - c0);
         if ((rc = d2r_reserve(ctx, ctx->pix, (size_t)nc * 3 * S * S * 4))) return rc;
@@ -897,15 +922,6 @@ static int ensure_pipeline(d2r_ctx *ctx, bool need_copy)
     for (hipEvent_t *e : all)
         if (!*e) D2R_HIP(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     return D2R_OK;
-}
-
-// Candidates per pass when frames leave the GPU: two pinned staging buffers of at most 1 GiB each.
-static uint32_t frame_pass_size(uint32_t per, size_t px)
-{
-    const uint64_t fit = std::max<uint64_t>(64, (1ull << 30) / (px * 3));
-    uint64_t p = std::min<uint64_t>(per, fit);
-    if (p >= 256) p -= p % 256;
-    return (uint32_t)std::max<uint64_t>(1, p);
 }
 
 // Hands the frames of one finished chunk (in pinned buffer b) to the worker pool: PNG files and / or the copy into
@@ -948,11 +964,11 @@ static int render_score_body(d2r_ctx *ctx, const d2r_nerf *fg, const d2r_clip *c
                              uint32_t C, float logit_scale, float *logits_dev, uint8_t *frames_out, const d2r_frame_sink *sink)
 {
     int rc;
-    const ViewParams V = d2r_view_params(view);
+    ViewParams V = d2r_view_params(view);
     const size_t px = (size_t)V.W * V.H;
     const bool to_host = frames_out || (sink && sink->png_dir);
-    uint32_t per = pass_size(ctx, clip, px);
-    if (to_host) per = frame_pass_size(per, px);
+    uint32_t per = d2r_pass_size(ctx, clip, px);
+    if (to_host) per = d2r_frame_pass_size(per, px);
     const uint32_t nchunks = (K + per - 1) / per;
     ctx->last_pass = per;
     ctx->last_chunks = nchunks;
@@ -963,6 +979,7 @@ static int render_score_body(d2r_ctx *ctx, const d2r_nerf *fg, const d2r_clip *c
     const size_t patch_bytes = d2r_clip_patch_bytes(clip, cap);
     if ((rc = d2r_reserve(ctx, ctx->cams, (size_t)cap * 48))) return rc;
     if ((rc = d2r_reserve_render(ctx, (size_t)cap * px))) return rc;          // queue, and the ray sort's second queue + bin counts
+    if ((rc = d2r_lens_table(ctx, V))) return rc;                             // a view with a lens: its table, built (and synchronised) here on a new view
     if ((rc = d2r_reserve(ctx, ctx->frames, (size_t)cap * px * 3))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->clipws[6], patch_bytes))) return rc;
     if (two && (rc = d2r_reserve(ctx, ctx->patches2, patch_bytes))) return rc;
@@ -1158,7 +1175,7 @@ int d2r_render_score(d2r_ctx *ctx, const d2r_nerf *fg, const d2r_clip *clip, con
     int rc = check_render_score_args(ctx, fg, clip, view, obj_pose_now, cam_pose, obj_poses_dev, logits_dev, nullptr);
     if (rc) return rc;
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = upload_text(ctx, clip, text_embeds, C))) return rc;
+    if ((rc = d2r_upload_text(ctx, clip, text_embeds, C))) return rc;
     return render_score_core(ctx, fg, clip, view, obj_pose_now, cam_pose, obj_poses_dev, K, C, logit_scale, logits_dev,
                              frames_out, nullptr);
 }
@@ -1172,7 +1189,7 @@ int d2r_render_score_host(d2r_ctx *ctx, const d2r_nerf *fg, const d2r_clip *clip
     if (rc) return rc;
     if (K == 0) return D2R_OK;
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = upload_text(ctx, clip, text_embeds, C))) return rc;
+    if ((rc = d2r_upload_text(ctx, clip, text_embeds, C))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->poses, (size_t)K * 64))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->logits, (size_t)K * C * 4))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(ctx->poses.p, obj_poses, (size_t)K * 64, hipMemcpyHostToDevice, ctx->stream));

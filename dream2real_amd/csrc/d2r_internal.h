@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -161,15 +162,16 @@ struct d2r_ctx {
     int64_t overlap = 0;        // 1: render half of chunk i+1 on render_stream under the ViT of chunk i (measured neutral: both sides fill whole CUs); 0: program order on `stream`
     int64_t debug_fail_chunk = -1;   // fault injection for the error path of render_score_core (tests/test_api_path.py)
     uint32_t last_chunks = 0;   // chunks of the last d2r_render_score (its per-chunk counters are behind counters+64)
-    int64_t chunk = 4096;       // candidates per pass (capped per model/view by pass_size() in api.hip)
+    int64_t chunk = 4096;       // candidates per pass (capped per model/view by d2r_pass_size() in api.hip)
     uint32_t last_pass = 0;     // pass size the last d2r_render_score used (for its stats read-back)
     int64_t march_blocks = 0;  // 0 = auto
     int64_t ray_sort = 1;      // 1: the ray queue is sorted by the object region (Morton cell of the occupied box) a ray's first sample lies in before it is marched; 0: marched in generation order
     int64_t ray_sort_log2 = 4; // cells per axis = 2^this (1..4); measured 8^3 -> 16^3: another 6 %
     int64_t march_threads = 0; // threads per marcher workgroup: 0 = auto (768, or 512 when the HBM bricks exceed march_threads_auto_mib MiB), else 64 .. 768 in steps of 64
     int64_t march_threads_auto_mib = 64;   // apple 36 MB (issue-bound: 768 threads are 8 % faster), shelf 112 MB, 2.2x / 5x apple 394 / 89 MB (L2-miss-bound: 512 are 1-5 % faster)
-    uint32_t last_march_threads = 0, last_march_gbrick_bytes = 0;   // and the workgroup size / HBM-brick bytes of that launch
-    uint32_t last_march_nb = 0, last_march_ngb = 0;   // brick configuration the last march launch ran with (d2r_get_render_stats)
+    // read-backs (options march_threads_used, march_hbm_brick_bytes, march_lds_slots, march_hbm_brick_slots):
+    int64_t last_march_threads = 0, last_march_gbrick_bytes = 0;   // the workgroup size / HBM-brick bytes of the last march launch
+    int64_t last_march_nb = 0, last_march_ngb = 0;    // ... and the brick configuration it ran with
     int64_t refill_min = 64;   // measured on MI355X: a refill (queue + camera loads, ray setup, SH) costs several iterations,
                                // so a wave runs its 64 rays to the end (lane utilisation 0.79) rather than topping up at 16 free lanes (0.90)
     int64_t march_compact = 1; // marcher: compact a wave's last <= 32 rays into one tile (option "march_compact")
@@ -217,6 +219,16 @@ struct PerDeviceOnce {
 int d2r_fail(d2r_ctx *ctx, int code, const std::string &msg);
 int d2r_reserve(d2r_ctx *ctx, d2r_ctx::Buf &b, size_t bytes);
 
+// api.hip: what the entry points that score frames share
+struct d2r_clip;
+uint32_t d2r_pass_size(const d2r_ctx *, const d2r_clip *clip, size_t px);      // candidates per pass: option "chunk" under the model's (clip, optional) and the ray queue's (px per frame, 0 = no rays) 32-bit bounds
+uint32_t d2r_frame_pass_size(uint32_t per, size_t px);                        // ... bounded further when the frames of a pass leave the GPU
+int d2r_upload_text(d2r_ctx *, const d2r_clip *, const float *text, uint32_t C);   // checks the caller's [C][proj] text embeddings and queues them into ctx->text through a pinned slot
+// for each pass [c0, c0 + nc): fill(c0, nc) must leave nc frames [nc][h][w][3] in ctx->frames on ctx->stream
+int d2r_score_frames_chunked(d2r_ctx *, const d2r_clip *, uint32_t n, uint32_t w, uint32_t h, int rot90, uint32_t C, float logit_scale,
+                             const std::function<int(uint32_t c0, uint32_t nc)> &fill, float *logits_out, float *embeds_out /* optional */,
+                             uint8_t *frames_out /* optional */);
+
 #define D2R_HIP(ctx, expr)                                                              \
     do {                                                                                \
         hipError_t e_ = (expr);                                                         \
@@ -233,8 +245,8 @@ int d2r_launch_cameras_virtual(d2r_ctx *, const ViewParams &, const float *obj_n
                                float *cams_out);
 int d2r_launch_render(d2r_ctx *, const d2r_nerf *, const ViewParams &, const float *cams_dev,
                       uint32_t n, bool composite, float *rgba_dev, float *depth_dev,
-                      uint8_t *frames_dev, void *rects_dev = nullptr);
+                      uint8_t *frames_dev, void *rects_dev = nullptr);     // a view with a lens comes with its table attached (d2r_lens_table)
 int d2r_launch_bg_quantize(d2r_ctx *, uint32_t w, uint32_t h);
 ViewParams d2r_view_params(const d2r_view *v);
 int d2r_reserve_render(d2r_ctx *, size_t rays);    // ray queue (+ sorted copy and bin counts with the ray sort) for a pass of `rays` rays
-int d2r_lens_table(d2r_ctx *, ViewParams &V);      // attaches the view's undistorted-direction table (built on first use)
+int d2r_lens_table(d2r_ctx *, ViewParams &V);      // attaches the view's undistorted-direction table (built, and the stream synchronised, on a new view: call it before a chunk loop)

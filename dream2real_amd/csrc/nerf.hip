@@ -175,10 +175,10 @@ __global__ void k_cameras_virtual(ViewParams V, Mat16 obj_now, Mat16 cam, const 
 #ifndef D2R_MARCH_VAR
 #define D2R_MARCH_VAR 0                /* bit 0: LDS-brick addresses formed in fp32 (slot_addr_lds_f); bit 1: the next lattice point's occupancy word requested before the field evaluation */
 #endif
-#ifndef D2R_MARCH_RESERVE
 #ifndef D2R_MARCH_MLP2
 #define D2R_MARCH_MLP2 0               /* 1: both tiles of a wave iteration share every MLP weight fragment read (mlp_tile2) */
 #endif
+#ifndef D2R_MARCH_RESERVE
 #define D2R_MARCH_RESERVE 128          /* queue entries a wave reserves per atomic */
 #endif
 
@@ -1601,7 +1601,7 @@ ViewParams d2r_view_params(const d2r_view *v)
     V.near_distance = v->near_distance;
     V.lens_mode = v->lens_mode;
     for (int i = 0; i < 4; i++) V.lens[i] = v->lens_mode ? v->lens_params[i] : 0.f;
-    V.lens_tab = nullptr;           // d2r_launch_render attaches the view's table
+    V.lens_tab = nullptr;           // d2r_lens_table attaches the view's table
     return V;
 }
 
@@ -1630,7 +1630,9 @@ int d2r_launch_cameras_virtual(d2r_ctx *ctx, const ViewParams &V, const float *o
 
 // counters layout: [0] queue count, [1] queue head, [2..3] 64-bit sample counter
 // the [H][W] table of undistorted camera-space directions of a view with a lens: rebuilt only when the view's size, intrinsics
-// or coefficients change (once per task in the path), then synchronised so that any stream of the context may read it
+// or coefficients change (once per task in the path), then synchronised so that any stream of the context may read it.  Every
+// caller of d2r_launch_render attaches it BEFORE its chunk loop (and before render_score_body forks its streams): a rebuild
+// reserves memory and synchronises
 int d2r_lens_table(d2r_ctx *ctx, ViewParams &V)
 {
     V.lens_tab = nullptr;
@@ -1666,14 +1668,14 @@ int d2r_reserve_render(d2r_ctx *ctx, size_t rays)
     return D2R_OK;
 }
 
-int d2r_launch_render(d2r_ctx *ctx, const d2r_nerf *m, const ViewParams &V_in, const float *cams_dev, uint32_t n,
+int d2r_launch_render(d2r_ctx *ctx, const d2r_nerf *m, const ViewParams &V, const float *cams_dev, uint32_t n,
                       bool composite, float *rgba_dev, float *depth_dev, uint8_t *frames_dev, void *rects_dev)
 {
-    ViewParams V = V_in;
     const size_t rays = (size_t)n * V.W * V.H;
     if (rays >= (1ull << 32)) return d2r_fail(ctx, D2R_ERR_INVALID, "too many rays in one pass");
+    if (V.lens_mode == D2R_LENS_OPENCV && !V.lens_tab)
+        return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_launch_render: a view with a lens arrived without its table (d2r_lens_table)");
     int rc;
-    if ((rc = d2r_lens_table(ctx, V))) return rc;
     if ((rc = d2r_reserve_render(ctx, rays))) return rc;      // no-op when the caller sized the pass up front (render_score_core)
     if ((rc = d2r_reserve(ctx, ctx->counters, 64))) return rc;
     uint32_t *cnt = (uint32_t *)ctx->counters.p;

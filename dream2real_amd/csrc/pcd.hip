@@ -18,17 +18,6 @@
 
 #include "d2r_internal.h"
 
-// implemented in clip.hip / api.hip
-struct d2r_clip;
-int d2r_launch_preprocess(d2r_ctx *, d2r_clip *, const uint8_t *frames_dev, uint32_t n, uint32_t w, uint32_t h,
-                          int rot90, uint16_t *patches_dev, float *pixel_values_dev, const void *rects_dev = nullptr,
-                          const uint16_t *bg_patches_dev = nullptr, bool touched_only = false);
-int d2r_clip_forward(d2r_ctx *, const d2r_clip *, const uint16_t *patches_dev, uint32_t n, const float *text_dev,
-                     uint32_t C, float logit_scale, float *logits_dev, float *embeds_dev, const ClipL0Reuse *reuse = nullptr);
-size_t d2r_clip_patch_bytes(const d2r_clip *, uint32_t n);
-uint32_t d2r_clip_proj_dim(const d2r_clip *);
-uint32_t d2r_clip_max_images(const d2r_clip *);
-
 struct d2r_pcd {
     int device = 0;
     uint32_t n = 0;
@@ -293,12 +282,9 @@ int pcd_prepare(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const d2r_pc
     return D2R_OK;
 }
 
-// candidates k0 .. k0 + nc - 1 -> ctx->frames [nc][H][W][3]
+// candidates k0 .. k0 + nc - 1 -> ctx->frames [nc][H][W][3] (reserved by the caller for its largest pass)
 int pcd_candidates(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const PcdCam &c, uint32_t k0, uint32_t nc)
 {
-    const size_t px = (size_t)c.W * c.H;
-    int rc = d2r_reserve(ctx, ctx->frames, (size_t)nc * px * 3);
-    if (rc) return rc;
     hipLaunchKernelGGL(k_pcd_candidates, dim3(nc), dim3(PCD_THREADS), 0, ctx->stream, mv->xyz, mv->n, bg->n, (const uint32_t *)ctx->pcd_cols.p,
                        (const PcdMat *)ctx->pcd_mats.p + k0, c, (const unsigned long long *)ctx->pcd_bg_keys.p,
                        (const uint8_t *)ctx->pcd_bg_frame.p, (uint8_t *)ctx->frames.p);
@@ -355,7 +341,8 @@ int d2r_pcd_render(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *movable, cons
     int rc = pcd_prepare(ctx, bg, movable, view, cam_pose, obj_pose_now, obj_poses, K, c);
     if (rc) return rc;
     const size_t fb = (size_t)c.W * c.H * 3;
-    const uint32_t per = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(ctx->chunk, (int64_t)((1ull << 30) / fb)));
+    const uint32_t per = d2r_frame_pass_size(d2r_pass_size(ctx, nullptr, 0), (size_t)c.W * c.H);
+    if ((rc = d2r_reserve(ctx, ctx->frames, (size_t)std::min(per, K) * fb))) return rc;
     for (uint32_t k0 = 0; k0 < K; k0 += per) {
         const uint32_t nc = std::min(per, K - k0);
         if ((rc = pcd_candidates(ctx, bg, movable, c, k0, nc))) return rc;
@@ -370,36 +357,14 @@ int d2r_pcd_render_score_host(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mo
                               uint32_t K, const float *text_embeds, uint32_t C, float logit_scale, float *logits_out,
                               uint8_t *frames_out)
 {
-    if (!clip || (K && !logits_out)) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
-    if (!text_embeds || C == 0 || C > 1024) return d2r_fail(ctx, D2R_ERR_INVALID, "bad text embeddings");
-    PcdCam c;
-    int rc = pcd_prepare(ctx, bg, movable, view, cam_pose, obj_pose_now, obj_poses, K, c);
+    if (!ctx || !clip || (K && !logits_out)) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
+    D2R_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = d2r_upload_text(ctx, clip, text_embeds, C);      // (the text is checked before the point clouds and the view, as ever)
     if (rc) return rc;
-    const uint32_t D = d2r_clip_proj_dim(clip);
-    if ((rc = d2r_reserve(ctx, ctx->text, (size_t)C * D * 4))) return rc;
-    D2R_HIP(ctx, hipMemcpyAsync(ctx->text.p, text_embeds, (size_t)C * D * 4, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t fb = (size_t)c.W * c.H * 3;
-    // candidates per pass exactly as d2r_clip_score_frames picks them (api.hip pass_size without a pixel bound)
-    const uint32_t per = (uint32_t)std::min<uint64_t>((uint64_t)std::max<int64_t>(1, ctx->chunk), d2r_clip_max_images(clip));
-    for (uint32_t k0 = 0; k0 < K; k0 += per) {
-        const uint32_t nc = std::min(per, K - k0);
-        if ((rc = pcd_candidates(ctx, bg, movable, c, k0, nc))) return rc;
-        if ((rc = d2r_reserve(ctx, ctx->clipws[6], d2r_clip_patch_bytes(clip, nc)))) return rc;
-        if ((rc = d2r_reserve(ctx, ctx->logits, (size_t)nc * (C + D) * 4))) return rc;
-        float *lg = (float *)ctx->logits.p, *em = lg + (size_t)nc * C;
-        if ((rc = d2r_launch_preprocess(ctx, (d2r_clip *)clip, (const uint8_t *)ctx->frames.p, nc, c.W, c.H, 1,
-                                        (uint16_t *)ctx->clipws[6].p, nullptr)))
-            return rc;
-        if ((rc = d2r_clip_forward(ctx, clip, (const uint16_t *)ctx->clipws[6].p, nc, (const float *)ctx->text.p, C,
-                                   logit_scale, lg, em)))
-            return rc;
-        D2R_HIP(ctx, hipMemcpyAsync(logits_out + (size_t)k0 * C, lg, (size_t)nc * C * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (frames_out)
-            D2R_HIP(ctx, hipMemcpyAsync(frames_out + (size_t)k0 * fb, ctx->frames.p, (size_t)nc * fb, hipMemcpyDeviceToHost, ctx->stream));
-        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return D2R_OK;
+    PcdCam c;
+    if ((rc = pcd_prepare(ctx, bg, movable, view, cam_pose, obj_pose_now, obj_poses, K, c))) return rc;
+    auto fill = [&](uint32_t k0, uint32_t nc) { return pcd_candidates(ctx, bg, movable, c, k0, nc); };
+    return d2r_score_frames_chunked(ctx, clip, K, (uint32_t)c.W, (uint32_t)c.H, 1, C, logit_scale, fill, logits_out, nullptr, frames_out);
 }
 
 }  // extern "C"

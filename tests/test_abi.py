@@ -55,6 +55,77 @@ def test_product_does_not_use_oracle():
     assert "oracle" not in deps
 
 
+def _documented_options():
+    """include/d2r.h's option list (the comment above d2r_ctx_set_option): key -> (default, (lo, hi) or None).  The list writes a
+    key as `"key" (default D, LO..HI)`, the range being optional; "timing" is written `(0/1/2)` and "ln_fold" spells its
+    modes 0 .. 4 out in prose."""
+    h = open(os.path.join(REPO, "include", "d2r.h")).read()
+    doc = h[h.index("/* Tunables;"):h.index("D2R_API int d2r_ctx_set_option")]
+    opts = {}
+    for m in re.finditer(r'"(\w+)" \(default (-?\d+)(?:,\s*(?:\*\s*)?(\d+)\.\.(\d+)\))?', doc):
+        opts[m.group(1)] = (int(m.group(2)), (int(m.group(3)), int(m.group(4))) if m.group(3) else None)
+    assert '"timing" (0/1/2)' in doc and re.search(r'"ln_fold" \(default 4\)[^"]*?0: LayerNorm kernels[^"]*?4 \(default\)', doc, re.S)
+    opts["timing"] = (0, (0, 2))
+    opts["ln_fold"] = (opts["ln_fold"][0], (0, 4))
+    return opts
+
+
+def test_documented_options_are_parsed_from_the_header():
+    opts = _documented_options()
+    assert len(opts) == 25, sorted(opts)           # every key a product build can set
+    assert opts["chunk"] == (4096, (1, 16384)) and opts["lds_slots_max"] == (5, (0, 5)) and opts["debug_fail_chunk"] == (-1, None)
+    assert opts["overlap"] == (0, None) and opts["gbrick_max_mib"] == (512, (0, 512)) and opts["attn_rem"] == (1, (0, 4))
+
+
+@pytest.mark.gpu
+def test_every_documented_option_round_trips():
+    """One table serves d2r_ctx_set_option and d2r_ctx_get_option: every key include/d2r.h documents reads back its documented
+    default on a fresh context and a value that was set; a value outside a documented range is D2R_ERR_INVALID and leaves the
+    stored one alone; the read-backs of the last march launch can be read and not set; a product build refuses the
+    development builds' experiment switches in both directions (a development build round-trips them like any other key)."""
+    C = ctypes
+    lib = _lib.load()
+    from dream2real_amd import engine
+    ctx = engine.Context(0)
+    h = ctx.h
+    INVALID = -1
+    v = C.c_int64(-7)
+
+    def get(key):
+        v.value = -7
+        assert lib.d2r_ctx_get_option(h, key.encode(), C.byref(v)) == 0, key
+        return v.value
+
+    def put(key, value):
+        return lib.d2r_ctx_set_option(h, key.encode(), C.c_int64(value))
+
+    for key, (default, rng) in sorted(_documented_options().items()):
+        assert get(key) == default, key
+        if key == "march_threads":                 # 0 = auto, else a multiple of 64 up to the compiled size
+            ok, bad = [512, 64, 0], [-64, 100, 832, 2048]
+        elif rng:
+            ok, bad = [rng[1], rng[0]], [rng[0] - 1, rng[1] + 1]
+        else:
+            ok, bad = [0 if default else 1], []
+        for value in ok:
+            assert put(key, value) == 0 and get(key) == value, (key, value)
+        for value in bad:
+            assert put(key, value) == INVALID and get(key) == ok[-1], (key, value)
+        assert put(key, default) == 0 and get(key) == default, key
+    for key in ("march_lds_slots", "march_hbm_brick_slots", "march_hbm_brick_bytes", "march_threads_used"):
+        assert get(key) == 0                       # no march launch on this context yet
+        assert put(key, 1) == INVALID and get(key) == 0, key
+    stamp = os.path.join(REPO, "dream2real_amd", "csrc", "_build", "flags.stamp")       # the flags libd2r.so was built with
+    dev = os.path.exists(stamp) and "-DD2R_DEV" in open(stamp).read()
+    for key, value in (("gemm_cfg", 3), ("gemm_group", 4), ("gemm_stagger", 1)):
+        if dev:
+            assert put(key, value) == 0 and get(key) == value, key
+        else:
+            assert put(key, value) == INVALID, key
+            assert lib.d2r_ctx_get_option(h, key.encode(), C.byref(v)) == INVALID, key
+    ctx.close()
+
+
 @pytest.mark.gpu
 def test_bad_arguments_return_error_codes():
     """include/d2r.h: every function returns a negative d2r_status on bad input, with a message in d2r_last_error — no

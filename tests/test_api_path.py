@@ -187,14 +187,17 @@ def test_convert_poses_writes_render_transforms(tmp_path):
 
 # ------------------------------------------------------------------ GPU
 
-def _setup(W=96, H=54, clip="vit_tiny"):
+def _setup(W=96, H=54, clip="vit_tiny", lens=None):
     from dream2real_amd import engine
     from dream2real_amd.clip_model import CLIP_CONFIGS, random_clip_state_dict
     from synthetic_scenes import make_scene, make_task, scene_text_embeds
-    scene = make_scene("shopping")
+    scene = make_scene("shopping", lens=lens)
     ctx = engine.Context(0)
-    fg, bg = engine.Testbed(ctx, scene.fg), engine.Testbed(ctx, scene.bg)
-    fg.background_color = list(scene.fg_background)
+    if lens is None:
+        fg, bg = engine.Testbed(ctx, scene.fg), engine.Testbed(ctx, scene.bg)
+        fg.background_color = list(scene.fg_background)
+    else:
+        fg, bg = scene.testbeds(ctx)            # with the scene's training views: their lens is the render lens, as in smoke()
     cfg = CLIP_CONFIGS[clip]
     sc = engine.ClipScorer(ctx, cfg, random_clip_state_dict(cfg, seed=6))
     task = make_task(scene, fg, bg)
@@ -207,16 +210,29 @@ def test_fused_call_is_bit_identical_to_render_then_score(tmp_path):
     """renderer.render_score (one d2r_render_score_host call: 5 chunks of 16 through the two-stream pipeline, frames
     streamed back through the pinned double buffer, PNGs written by the library) == renderer.render + score_frames:
     frames, logits and files bit for bit, with the pipeline's overlap on and off."""
+    _check_fused_call_against_render_then_score(tmp_path, lens=None)
+
+
+@pytest.mark.gpu
+def test_fused_call_through_a_lens_is_bit_identical_to_render_then_score(tmp_path):
+    """The same on the scene smoke() uses, whose views carry the reference configs' OpenCV lens: the view's table of
+    undistorted directions is built once before the chunk loop, and one chunk / several chunks / overlap on all read it."""
+    from dream2real_amd.scene import DEMO_LENS
+    _check_fused_call_against_render_then_score(tmp_path, lens=DEMO_LENS)
+
+
+def _check_fused_call_against_render_then_score(tmp_path, lens):
     from PIL import Image
     from dream2real_amd import combined_rendering
     from dream2real_amd.accio2ngp import converter
     from dream2real_amd.obj_pose_opt import sample_poses_grid
     from dream2real_amd.virtual_cam_pose_sample import get_virtual_cam_poses
-    scene, ctx, fg, bg, sc, task, text = _setup()
+    scene, ctx, fg, bg, sc, task, text = _setup(lens=lens)
     poses = converter(sample_poses_grid(task, [9, 8, 1, 1, 1, 1], scene.scene_type).reshape(-1, 4, 4))      # 72
     rp = converter(get_virtual_cam_poses(task, [0]))
     rend = combined_rendering.renderer(str(tmp_path), task, resolution=(96, 54))
     frames_ref = np.stack(rend.render(poses, rp, [0], save=False))
+    assert bool(rend._last[0].lens_mode) == (lens is not None)      # the lens reached the view the library renders
     logits_ref = sc.score_frames(frames_ref, text, rot90=True)
     ctx.set_option("chunk", 16)
     for overlap in (1, 0):
