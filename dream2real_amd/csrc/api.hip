@@ -196,6 +196,7 @@ static const Option g_options[] = {
     {"lds_slots_max", &d2r_ctx::lds_slots_max, Option::RANGE, 0, 5},      // read by d2r_nerf_create: set it before creating the model
     {"gbrick_max_mib", &d2r_ctx::gbrick_max_mib, Option::RANGE, 0, 512},  // read by d2r_nerf_create too
     {"mlp_f16", &d2r_ctx::mlp_f16, Option::FLAG},
+    {"render_arith", &d2r_ctx::render_arith, Option::RANGE, 0, 2},
     {"bricks", &d2r_ctx::use_bricks, Option::FLAG},
     {"raygen_rect", &d2r_ctx::raygen_rect, Option::FLAG},
     {"timing", &d2r_ctx::timing, Option::RANGE, 0, 2, 0, opt_timing},

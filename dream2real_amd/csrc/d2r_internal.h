@@ -183,6 +183,7 @@ struct d2r_ctx {
     int64_t cls_last = 1;          // vision tower: run the last block on the class-token rows only (the head reads nothing else)
     int64_t gemm_cfg = 0;      // experiment switch for the GEMM tile configuration (0 = default)
     int64_t mlp_f16 = 1;       // operand type of the NeRF MLPs' MFMAs: 1 (default since round 6) fp16 — the reference's operand type (tiny-cuda-nn), the snapshot's weights unrounded; 0 bf16 (north_star's wording).  Same MFMA rate; chosen by the distance table of tests/test_gpu_parity.py::test_render_distances_to_the_fp16_accumulation_emulation
+    int64_t render_arith = 0;  // arithmetic of the field evaluation (nerf.hip eval_wave<…, ARITH>): 0 the specification (fp32 accumulation); 1 / 2 oracle/d2r_oracle.c's d2r_oracle_set_arith(1 / 2) restated — hash-grid corners summed in half (2: the fma form), half accumulators in both MLPs (one rounding per 16-wide k-step), half activations.  A validation mode: brick-free kernels, fp16 operands whatever mlp_f16 says
     int64_t use_bricks = 1;
     int64_t raygen_rect = 1;   // composite mode: generate rays only inside the projected occupied bbox
     int64_t gbrick_slots = 8;  // at most this many slots use HBM bricks

@@ -935,6 +935,54 @@ __device__ __forceinline__ void slot_blend(const uint32_t *raw, const float *w, 
     o1 = a1;
 }
 
+// fp32 operation, then ONE round-to-nearest-even conversion to half (subnormal halves kept: the kernels run with fp16 denormals on).
+// The empty asm keeps the fp32 result in a register of its own (no instruction): without it hipcc fuses the convert into the operation
+// — fptrunc(fma) becomes v_fma_mixlo_f16 — and that instruction rounds the exact result ONCE, to half, where the definition rounds
+// to fp32 first: measured on MI355X, 2 .. 11 of 20 000 features off by one half ulp in the fma form (tests/test_render_arith_gpu.py
+// test_grid_encoding_is_bit_exact).
+__device__ __forceinline__ float rn16(float x)
+{
+    asm("" : "+v"(x));
+    return (float)(_Float16)x;
+}
+
+// The same blend in tiny-cuda-nn's half arithmetic (option "render_arith" 1 / 2; oracle/d2r_oracle.c hashgrid_encode under
+// d2r_oracle_set_arith, operation by operation): one accumulator per feature from 0, corners c = 0 .. 7 in that order (bit d of
+// c chooses dimension d: the order of raw[] on every path), the fp32 weight built as ((1 wx) wy) wz,
+//   ARITH 1: acc = rn16(acc + rn16(weight val))        ARITH 2: acc = rn16(fmaf(rn16(weight), val, acc))
+// Held bit-exact against the oracle (test_grid_encoding_is_bit_exact).  A validation mode: scalar converts and adds, no packed tricks.
+template <int ARITH>
+__device__ __forceinline__ void slot_blend_half(const uint32_t *raw, const float *w, float &o0, float &o1)
+{
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        float wc = 1.0f;
+#pragma unroll
+        for (int d = 0; d < 3; d++) wc *= (c & (1 << d)) ? w[d] : 1.0f - w[d];
+        union { uint32_t u; f16x2 v; } e;
+        e.u = raw[c];
+        const float v0 = (float)e.v[0], v1 = (float)e.v[1];
+        if constexpr (ARITH == 1) {
+            a0 = rn16(a0 + rn16(wc * v0));
+            a1 = rn16(a1 + rn16(wc * v1));
+        } else {
+            const float wh = rn16(wc);
+            a0 = rn16(fmaf(wh, v0, a0));
+            a1 = rn16(fmaf(wh, v1, a1));
+        }
+    }
+    o0 = a0;
+    o1 = a1;
+}
+template <int ARITH>
+__device__ __forceinline__ void slot_blend_as(const uint32_t *raw, const float *w, float &o0, float &o1)
+{
+    if constexpr (ARITH == 0) slot_blend(raw, w, o0, o1);
+    else slot_blend_half<ARITH>(raw, w, o0, o1);
+}
+
 // compile-time loop: f(std::integral_constant<int, B>{}), ..., f(std::integral_constant<int, E - 1>{})
 template <int B, int E, class F>
 __device__ __forceinline__ void static_for(F &&f)
@@ -950,7 +998,7 @@ __device__ __forceinline__ void static_for(F &&f)
 // LDS-brick slots) while those are in flight, then the blends.  Slots below NB + NGB come from dense HBM bricks, where the two
 // x-neighbour corners are adjacent words: ONE 8-byte gather per (y, z) pair halves the lane-gathers (the texture addresser's
 // cost is per lane); the others from the slot tables (dense / hashed / mixed by ND).
-template <int NB, int NGB, int ND, int S0, int CNT, class Under>
+template <int NB, int NGB, int ND, int S0, int CNT, int ARITH, class Under>
 __device__ __forceinline__ void encode_batch(const NerfParams &P, const __amdgpu_buffer_rsrc_t &rs, const __amdgpu_buffer_rsrc_t &rsb,
                                              bool hi, float x, float y, float z, float *f, Under &&under)
 {
@@ -982,14 +1030,14 @@ __device__ __forceinline__ void encode_batch(const NerfParams &P, const __amdgpu
     under();
     static_for<0, CNT>([&](auto j) {
         constexpr int J = decltype(j)::value, I = S0 + J;
-        slot_blend(raw[J], w[J], f[2 * I], f[2 * I + 1]);
+        slot_blend_as<ARITH>(raw[J], w[J], f[2 * I], f[2 * I + 1]);
     });
 }
 
 // global slots S0 .. 7 in batches: at most four slots per batch while they are bricks (4 address registers per slot survive
 // into the load phase: the base and three strides are shared), at most three once table slots (eight independent
 // addresses each, plus the dense / hashed index arithmetic) are among them
-template <int NB, int NGB, int ND, int S0, class Under>
+template <int NB, int NGB, int ND, int S0, int ARITH, class Under>
 __device__ __forceinline__ void encode_from(const NerfParams &P, const __amdgpu_buffer_rsrc_t &rs, const __amdgpu_buffer_rsrc_t &rsb,
                                             bool hi, float x, float y, float z, float *f, Under &&under)
 {
@@ -998,8 +1046,8 @@ __device__ __forceinline__ void encode_from(const NerfParams &P, const __amdgpu_
     // split the remainder evenly over the batches it needs (5 -> 3 + 2, 8 -> 3 + 3 + 2 or 4 + 4)
     constexpr int NBATCH = (LEFT + BMAX - 1) / BMAX;
     constexpr int CNT = (LEFT + NBATCH - 1) / NBATCH;
-    encode_batch<NB, NGB, ND, S0, CNT>(P, rs, rsb, hi, x, y, z, f, under);
-    if constexpr (LEFT > CNT) encode_from<NB, NGB, ND, S0 + CNT>(P, rs, rsb, hi, x, y, z, f, [] {});
+    encode_batch<NB, NGB, ND, S0, CNT, ARITH>(P, rs, rsb, hi, x, y, z, f, under);
+    if constexpr (LEFT > CNT) encode_from<NB, NGB, ND, S0 + CNT, ARITH>(P, rs, rsb, hi, x, y, z, f, [] {});
 }
 
 // All 8 slots of one sample.  f[2*i], f[2*i+1] = features of slot i (this lane's level of the pair).  Matches oracle
@@ -1008,7 +1056,7 @@ __device__ __forceinline__ void encode_from(const NerfParams &P, const __amdgpu_
 // registers per slot live (8 offsets, 3 fractions, 8 gathered words) across its three phases, and with 5 .. 8 slots in ONE
 // batch the 168-register budget of three waves per SIMD spilled 6 .. 90 registers inside the march loop (round 5: the
 // generic no-brick kernel had always run like that).
-template <int NB, int NGB, int ND, bool F16>
+template <int NB, int NGB, int ND, bool F16, int ARITH = 0>
 __device__ __forceinline__ void encode_sample(const NerfParams &P, const __amdgpu_buffer_rsrc_t &rs,
                                               const __amdgpu_buffer_rsrc_t &rsb,
                                               const uint8_t *__restrict__ lds_bricks, bool hi, float x, float y,
@@ -1040,7 +1088,7 @@ __device__ __forceinline__ void encode_sample(const NerfParams &P, const __amdgp
                 br[2 * j + 1] = p[1];
             }
 #endif
-            slot_blend(br, bw, f[2 * i], f[2 * i + 1]);
+            slot_blend_as<ARITH>(br, bw, f[2 * i], f[2 * i + 1]);
         }
     };
 #if D2R_MARCH_ABLATE & 3
@@ -1048,10 +1096,10 @@ __device__ __forceinline__ void encode_sample(const NerfParams &P, const __amdgp
     for (int i = 0; i < 16; i++) f[i] = x + (float)i * y;
     if (!(D2R_MARCH_ABLATE & 1)) lds_slots();
     if constexpr (NG != 0)
-        if (!(D2R_MARCH_ABLATE & 2)) encode_from<NB, NGB, ND, NB>(P, rs, rsb, hi, x, y, z, f, [] {});
+        if (!(D2R_MARCH_ABLATE & 2)) encode_from<NB, NGB, ND, NB, ARITH>(P, rs, rsb, hi, x, y, z, f, [] {});
 #else
     if constexpr (NG == 0) lds_slots();
-    else encode_from<NB, NGB, ND, NB>(P, rs, rsb, hi, x, y, z, f, lds_slots);
+    else encode_from<NB, NGB, ND, NB, ARITH>(P, rs, rsb, hi, x, y, z, f, lds_slots);
 #endif
     // straight into the two bf16 B fragments of density layer 1 (k-step 0: slots 0..3, 1: slots 4..7)
     p0.x = pack2<F16>(f[0], f[1]); p0.y = pack2<F16>(f[2], f[3]); p0.z = pack2<F16>(f[4], f[5]); p0.w = pack2<F16>(f[6], f[7]);
@@ -1223,6 +1271,62 @@ __device__ __forceinline__ void mlp_tile2(const uint4 *__restrict__ sw, uint32_t
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// One tile through both MLPs with HALF accumulators (option "render_arith" 1 / 2; oracle/d2r_oracle.c matvec_f16_halfacc / nerf_eval):
+// one v_mfma_f32_32x32x16_f16 has K = 16, so one MFMA from a ZERO accumulator is one 16-wide k-step's sum of exact products (the
+// oracle's `part`); a VALU add and a convert round it into the running half accumulator, acc = rn16(acc + part).  The fragment order
+// puts inputs 16 s .. 16 s + 15 into k-step s (build_frag), the oracle's own grouping.  Inputs are halves already (grid features, SH
+// rounded by pack2, the previous layer's half results, so relu_pack's conversion is exact), the activation acts on the half result,
+// network outputs are halves.  The MFMA's order of the 16 products inside a k-step is not the oracle's fmaf chain: `part` can differ
+// in its last fp32 bit and flip a half rounding that sits on a tie — held to a tolerance, not bit-exact.
+__device__ __forceinline__ void mlp_tile_half(const uint4 *__restrict__ sw, uint32_t lane, const uint4 &a0, const uint4 &a1, const uint4 &sh, float *out)
+{
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // one 32-output half of a layer: NK weight fragments from sw[W0], inputs x[0 .. NK)
+    auto half_layer = [&](int W0, int NK, const uint4 *x) {
+        f32x16 acc = zero;
+#pragma unroll
+        for (int i = 0; i < NK; i++) {
+            const f32x16 part = mfma<true>(sw[(W0 + i) * 64 + lane], x[i], zero);
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[r] = rn16(acc[r] + part[r]);
+        }
+        return acc;
+    };
+    uint4 x[4], p[4];
+    f32x16 g;
+    // density layer 1: 64 x 32
+    x[0] = a0; x[1] = a1;
+    g = half_layer(0, 2, x);
+    p[0] = relu_pack<true>(g, 0); p[1] = relu_pack<true>(g, 8);
+    g = half_layer(2, 2, x);
+    p[2] = relu_pack<true>(g, 0); p[3] = relu_pack<true>(g, 8);
+    __builtin_amdgcn_sched_barrier(0);
+    // density layer 2: 16 (padded 32) x 64
+    g = half_layer(4, 4, p);
+    out[0] = g[0];
+    // colour layer 1: 64 x 32, input = [density out (no activation) | SH]
+    x[0].x = pack2<true>(g[0], g[1]); x[0].y = pack2<true>(g[2], g[3]); x[0].z = pack2<true>(g[4], g[5]); x[0].w = pack2<true>(g[6], g[7]);
+    x[1] = sh;
+    __builtin_amdgcn_sched_barrier(0);
+    g = half_layer(8, 2, x);
+    p[0] = relu_pack<true>(g, 0); p[1] = relu_pack<true>(g, 8);
+    g = half_layer(10, 2, x);
+    p[2] = relu_pack<true>(g, 0); p[3] = relu_pack<true>(g, 8);
+    __builtin_amdgcn_sched_barrier(0);
+    // colour layer 2: 64 x 64
+    g = half_layer(12, 4, p);
+    x[0] = relu_pack<true>(g, 0); x[1] = relu_pack<true>(g, 8);
+    g = half_layer(16, 4, p);
+    x[2] = relu_pack<true>(g, 0); x[3] = relu_pack<true>(g, 8);
+    __builtin_amdgcn_sched_barrier(0);
+    // colour layer 3: 16 (padded 32) x 64
+    g = half_layer(20, 4, x);
+    out[1] = g[0];
+    out[2] = g[1];
+    out[3] = g[2];
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // SH fragments of the wave's ray directions: the colour net's second B fragment for tile 0
 // (directions of lanes 0..31) and tile 1 (lanes 32..63); this lane holds coefficients
 // 8hi..8hi+7.  Directions are per RAY, so k_march recomputes these only when it refills.
@@ -1246,7 +1350,9 @@ __device__ __forceinline__ void sh_fragments(uint32_t lane, float dx, float dy, 
 
 // Evaluate the wave's 64 samples (one per lane; `valid` marks lanes that have one).
 // On return every valid lane holds sigma and the network rgb of ITS OWN sample.
-template <int NB, int NGB, int ND, bool F16>
+// ARITH (option "render_arith"): 0 the specification, fp32 accumulation; 1 / 2 tiny-cuda-nn's half arithmetic as
+// oracle/d2r_oracle.c emulates it (slot_blend_half, mlp_tile_half), fp16 operands only.
+template <int NB, int NGB, int ND, bool F16, int ARITH = 0>
 __device__ __forceinline__ void eval_wave(const NerfParams &P, const __amdgpu_buffer_rsrc_t &rs,
                                           const __amdgpu_buffer_rsrc_t &rsb, const uint4 *__restrict__ sw,
                                           const uint8_t *__restrict__ lds_bricks, uint32_t lane, bool valid, float x,
@@ -1264,8 +1370,8 @@ __device__ __forceinline__ void eval_wave(const NerfParams &P, const __amdgpu_bu
     // this lane's levels: 2i + hi for every slot i (slots 0..3 -> k-step 0, 4..7 -> k-step 1);
     // the features go straight into bf16 fragments (8 registers per sample instead of 16 floats)
     uint4 fa0 = make_uint4(0, 0, 0, 0), fa1 = fa0, fb0 = fa0, fb1 = fa0;
-    if (av) encode_sample<NB, NGB, ND, F16>(P, rs, rsb, lds_bricks, hi, ax, ay, az, fa0, fa1);
-    if (bv) encode_sample<NB, NGB, ND, F16>(P, rs, rsb, lds_bricks, hi, bx, by, bz, fb0, fb1);
+    if (av) encode_sample<NB, NGB, ND, F16, ARITH>(P, rs, rsb, lds_bricks, hi, ax, ay, az, fa0, fa1);
+    if (bv) encode_sample<NB, NGB, ND, F16, ARITH>(P, rs, rsb, lds_bricks, hi, bx, by, bz, fb0, fb1);
     float oa[4] = {0.f, 0.f, 0.f, 0.f}, ob[4] = {0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_sched_barrier(0);
     // a tile none of whose 32 samples exists (the tail of a wave's rays, compacted into tile 0 by k_march) costs nothing:
@@ -1275,6 +1381,11 @@ __device__ __forceinline__ void eval_wave(const NerfParams &P, const __amdgpu_bu
     oa[0] = __uint_as_float(fa0.x) * 1e-3f; oa[1] = __uint_as_float(fa0.y); oa[2] = __uint_as_float(fa1.x); oa[3] = __uint_as_float(fa1.y);
     ob[0] = __uint_as_float(fb0.x) * 1e-3f; ob[1] = __uint_as_float(fb0.y); ob[2] = __uint_as_float(fb1.x); ob[3] = __uint_as_float(fb1.y);
 #else
+    if constexpr (ARITH != 0) {
+        static_assert(F16, "the half arithmetic has no bf16 form");
+        if ((uint32_t)vm != 0u) mlp_tile_half(sw, lane, fa0, fa1, shfA, oa);
+        if ((uint32_t)(vm >> 32) != 0u) mlp_tile_half(sw, lane, fb0, fb1, shfB, ob);
+    } else {
 #if D2R_MARCH_MLP2
     if ((uint32_t)vm != 0u && (uint32_t)(vm >> 32) != 0u) mlp_tile2<F16>(sw, lane, fa0, fa1, shfA, oa, fb0, fb1, shfB, ob);
     else if ((uint32_t)vm != 0u) mlp_tile<F16>(sw, lane, fa0, fa1, shfA, oa);
@@ -1283,6 +1394,7 @@ __device__ __forceinline__ void eval_wave(const NerfParams &P, const __amdgpu_bu
     if ((uint32_t)vm != 0u) mlp_tile<F16>(sw, lane, fa0, fa1, shfA, oa);
     if ((uint32_t)(vm >> 32) != 0u) mlp_tile<F16>(sw, lane, fb0, fb1, shfB, ob);
 #endif
+    }
 #endif
     // tile-1 results live in lanes 0..31; their owners are lanes 32..63
     float ts = __shfl_xor(ob[0], 32), tr = __shfl_xor(ob[1], 32), tg = __shfl_xor(ob[2], 32), tb = __shfl_xor(ob[3], 32);
@@ -1295,7 +1407,7 @@ __device__ __forceinline__ void eval_wave(const NerfParams &P, const __amdgpu_bu
 }
 
 // field evaluation at arbitrary points (parity hook used by tests through d2r_eval_points)
-template <int ND, bool F16>
+template <int ND, bool F16, int ARITH = 0>
 __global__ __launch_bounds__(256) void k_eval_points(NerfParams P, const float *__restrict__ xyz,
                                                      const float *__restrict__ dirs, uint32_t n,
                                                      float *__restrict__ out)
@@ -1315,7 +1427,7 @@ __global__ __launch_bounds__(256) void k_eval_points(NerfParams P, const float *
     float s, r, g, b;
     uint4 shfA, shfB;
     sh_fragments<F16>(lane, dx, dy, dz, shfA, shfB);
-    eval_wave<0, 0, ND, F16>(P, rs, rs, sw, nullptr, lane, valid, x, y, z, shfA, shfB, s, r, g, b);   // arbitrary points: no bricks
+    eval_wave<0, 0, ND, F16, ARITH>(P, rs, rs, sw, nullptr, lane, valid, x, y, z, shfA, shfB, s, r, g, b);   // arbitrary points: no bricks
     if (valid) *(float4 *)(out + 4 * (size_t)i) = make_float4(s, r, g, b);
 }
 
@@ -1326,7 +1438,7 @@ __global__ __launch_bounds__(256) void k_eval_points(NerfParams P, const float *
 #ifndef D2R_MARCH_THREADS
 #define D2R_MARCH_THREADS 768
 #endif
-template <bool COMPOSITE, int NB, int NGB, int ND, bool CONE = false, bool F16 = false>
+template <bool COMPOSITE, int NB, int NGB, int ND, bool CONE = false, bool F16 = false, int ARITH = 0>
 __global__ __launch_bounds__(D2R_MARCH_THREADS) void k_march(NerfParams P, ViewParams V, const float *__restrict__ cams,
                                                   const uint2 *__restrict__ queue,
                                                   const uint32_t *__restrict__ qcount,
@@ -1468,7 +1580,7 @@ __global__ __launch_bounds__(D2R_MARCH_THREADS) void k_march(NerfParams P, ViewP
 #endif
         // ---- evaluate this wave's samples
         float sigma, cr, cg, cb;
-        eval_wave<NB, NGB, ND, F16>(P, rs, rsb, sw, lds_bricks, lane, alive, px, py, pz, shfA, shfB, sigma, cr, cg, cb);
+        eval_wave<NB, NGB, ND, F16, ARITH>(P, rs, rsb, sw, lds_bricks, lane, alive, px, py, pz, shfA, shfB, sigma, cr, cg, cb);
 
         // ---- composite + advance
         if (alive) {
@@ -1753,6 +1865,9 @@ int d2r_launch_render(d2r_ctx *ctx, const d2r_nerf *m, const ViewParams &V, cons
         }
         if (none) nb = ngb = 0;
     }
+    // "render_arith" 1 / 2: the brick-free generic table kernel (a validation mode: two instantiations per mode, not thirty-four)
+    const int arith = (int)ctx->render_arith;
+    if (arith) nb = ngb = 0;
     NerfParams PP = m->P;
     PP.refill_min = (uint32_t)ctx->refill_min;
     PP.compact = (uint32_t)ctx->march_compact;
@@ -1765,16 +1880,16 @@ int d2r_launch_render(d2r_ctx *ctx, const d2r_nerf *m, const ViewParams &V, cons
     else if (!sort_log2 && ngb && m->P.gbrick_bytes > (size_t)ctx->march_threads_auto_mib << 20) threads = std::min<uint32_t>(512u, D2R_MARCH_THREADS);
 #define D2R_MARCH_C(COMP, NB, NGB, ND, CONE)                            \
     do {                                                                \
-        if (ctx->mlp_f16) D2R_MARCH_F(COMP, NB, NGB, ND, CONE, true);   \
-        else D2R_MARCH_F(COMP, NB, NGB, ND, CONE, false);               \
+        if (ctx->mlp_f16) D2R_MARCH_F(COMP, NB, NGB, ND, CONE, true, 0);   \
+        else D2R_MARCH_F(COMP, NB, NGB, ND, CONE, false, 0);               \
     } while (0)
-#define D2R_MARCH_F(COMP, NB, NGB, ND, CONE, F16)                                                                 \
+#define D2R_MARCH_F(COMP, NB, NGB, ND, CONE, F16, ARITH)                                                              \
     do {                                                                                                          \
         static PerDeviceOnce attr;                                                                                \
         attr.run(ctx->device, [] {                                                                                \
-            (void)hipFuncSetAttribute((const void *)k_march<COMP, NB, NGB, ND, CONE, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (CONE ? 512 : 0)); /* the CONE kernels hold 512 B of static LDS (cone tables): static + dynamic <= 160 KiB */ \
+            (void)hipFuncSetAttribute((const void *)k_march<COMP, NB, NGB, ND, CONE, F16, ARITH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (CONE ? 512 : 0)); /* the CONE kernels hold 512 B of static LDS (cone tables): static + dynamic <= 160 KiB */ \
         });                                                                                                       \
-        hipLaunchKernelGGL((k_march<COMP, NB, NGB, ND, CONE, F16>), dim3(blocks), dim3(threads), lds, ctx->stream, PP, V, cams_dev, q, \
+        hipLaunchKernelGGL((k_march<COMP, NB, NGB, ND, CONE, F16, ARITH>), dim3(blocks), dim3(threads), lds, ctx->stream, PP, V, cams_dev, q, \
                            cnt, cnt + 1, COMP ? nullptr : rgba_dev, COMP ? nullptr : depth_dev,                   \
                            COMP ? bgd : nullptr, COMP ? frames_dev : nullptr, sc);                                \
     } while (0)
@@ -1791,13 +1906,26 @@ int d2r_launch_render(d2r_ctx *ctx, const d2r_nerf *m, const ViewParams &V, cons
         D2R_MARCH_CASE(COMP, CONE, 0, 7) D2R_MARCH_CASE(COMP, CONE, 0, 6)                                                                   \
         else D2R_MARCH_C(COMP, 0, 0, 5, CONE);                          \
     } while (0)
+    // "render_arith" 1 / 2 have one kernel per (COMP, CONE): the generic table kernel with fp16 operands
+#define D2R_MARCH_HALF(COMP, CONE)                                      \
+    do {                                                                \
+        if (arith == 1) D2R_MARCH_F(COMP, 0, 0, -1, CONE, true, 1);     \
+        else D2R_MARCH_F(COMP, 0, 0, -1, CONE, true, 2);                \
+    } while (0)
+#define D2R_MARCH_ANY(COMP, CONE)                                       \
+    do {                                                                \
+        if (arith) D2R_MARCH_HALF(COMP, CONE);                          \
+        else D2R_MARCH_PICK(COMP, CONE);                                \
+    } while (0)
     if (cone) {
-        if (composite) D2R_MARCH_PICK(true, true);
-        else D2R_MARCH_PICK(false, true);
+        if (composite) D2R_MARCH_ANY(true, true);
+        else D2R_MARCH_ANY(false, true);
     } else {
-        if (composite) D2R_MARCH_PICK(true, false);
-        else D2R_MARCH_PICK(false, false);
+        if (composite) D2R_MARCH_ANY(true, false);
+        else D2R_MARCH_ANY(false, false);
     }
+#undef D2R_MARCH_ANY
+#undef D2R_MARCH_HALF
     ctx->last_march_nb = nb;
     ctx->last_march_ngb = ngb;
     ctx->last_march_threads = threads;
@@ -1824,7 +1952,9 @@ int d2r_launch_eval_points(d2r_ctx *ctx, const d2r_nerf *m, const float *xyz, co
                            float *out)
 {
     const dim3 g((n + 255) / 256), b(256);
-    if (m->P.n_dense == 5) {
+    if (ctx->render_arith == 1) hipLaunchKernelGGL((k_eval_points<-1, true, 1>), g, b, 0, ctx->stream, m->P, xyz, dirs, n, out);
+    else if (ctx->render_arith == 2) hipLaunchKernelGGL((k_eval_points<-1, true, 2>), g, b, 0, ctx->stream, m->P, xyz, dirs, n, out);
+    else if (m->P.n_dense == 5) {
         if (ctx->mlp_f16) hipLaunchKernelGGL((k_eval_points<5, true>), g, b, 0, ctx->stream, m->P, xyz, dirs, n, out);
         else hipLaunchKernelGGL((k_eval_points<5, false>), g, b, 0, ctx->stream, m->P, xyz, dirs, n, out);
     } else {

@@ -466,6 +466,18 @@ D2R_API int d2r_get_timing(d2r_ctx *ctx, d2r_timing *out);
  *     emulation of tiny-cuda-nn's half-accumulating arithmetic on a trained-like field the fp16-operand marcher sits where the fp32
  *     specification sits (|dlog sigma| 0.032 vs 0.030, no object pixel off by more than one LSB), the bf16-operand one twice as far
  *     (0.064, 9 % of the object's pixels) — DESIGN.md section 5.
+ * "render_arith" (0 default, 1, 2): arithmetic of the NeRF field evaluation, honoured by every entry point that marches (d2r_render,
+ *     d2r_render_composite, d2r_render_score, d2r_render_score_host) and by d2r_nerf_eval_points.  0: the specification — fp16
+ *     tables and weights, fp32 accumulation.  1: tiny-cuda-nn's half arithmetic as oracle/d2r_oracle.c emulates it
+ *     (d2r_oracle_set_arith(1)): the hash grid's eight corner terms summed in half, acc = half(acc + half(w v)) in corner order; both
+ *     MLPs with half accumulators, one rounding per 16-wide k-step (one fp16 MFMA from a zero accumulator, then a convert), half
+ *     activations and half network outputs; exp and sigmoid stay fp32.  2: the same with the grid's newer form,
+ *     acc = half(fma(half(w), v, acc)).  The grid part restates the emulation operation by operation; the MLPs sum a k-step's 16
+ *     products in the MFMA's order, not the emulation's, so a rounding that sits on a tie can fall the other way (DESIGN.md
+ *     section 5).  With 1 / 2 the MLP operands are fp16 whatever "mlp_f16" says: the half arithmetic has no bf16 form.  A
+ *     validation mode for telling arithmetic apart from other differences against a reference run's frames
+ *     (tools/validate_artifacts.py --search-forks): brick-free kernels, slower than 0.  Values outside 0..2 are
+ *     refused (D2R_ERR_INVALID) and the stored value stays.
  * "ln_fold" (default 4): schedule of the vision tower.  0: LayerNorm kernels between the GEMMs, fp32 residual
  *     stream.  1-3: LayerNorm folded into the QKV / fc1 GEMMs (LN(x) W^T + b = rstd (x (gamma o W)^T - mean
  *     colsum) + b'), row statistics emitted by the residual GEMMs' epilogues, which also write the bf16 operand

@@ -26,6 +26,13 @@ Sections (each runs when its inputs are present and says what it skipped otherwi
                   the reference recomputes from the scene instead of caching: --obj-pose / --cam-pose, 4x4 np.savetxt
                   files in the reference's world / OpenCV convention)
   (d) argmax      the best pose from (b)'s scores against goal_pose.txt
+  (e) forks       --search-forks: (c)'s sample of poses rendered under every combination of the believed forks that are runtime
+                  options on both sides — "render_arith" 0 / 1 / 2 (the specification, tiny-cuda-nn's half arithmetic, its fma grid
+                  form), "mlp_f16" 0 / 1 (with render_arith 0 only: modes 1 / 2 are fp16), the view's lens on / off — each compared
+                  with the PNGs (worst and mean PSNR, share of pixels off by more than one LSB); the table sorted by that share and
+                  the closest combination.  The options it sets (render_arith, mlp_f16, the Testbeds' lens switches) are put back; like
+                  (c) it leaves the Testbeds' view and the context's background where the last render put them.  Same inputs as
+                  (c); sets no bar of its own
 
 Prints a JSON report (also to --out).  Exit code 0 = every section that ran is within its bar, 1 = something is off,
 2 = nothing could run.  The product path only: nothing here touches oracle/.
@@ -89,6 +96,77 @@ def spearman(a, b):
     return float(np.corrcoef(ra, rb)[0, 1]) if len(a) > 2 else 1.0
 
 
+# ---------------- (e) the fork search.  fork_combinations / rank_forks / search_forks touch no GPU: `render` is any callable
+# combination -> frames and `options` anything with get_option / set_option, so tests drive them with fakes.
+
+def fork_combinations():
+    """Every combination of the forks that are runtime options: (render_arith, mlp_f16) in (0, 0), (0, 1), (1, -), (2, -) — the half
+    arithmetic has no bf16 form, mlp_f16 None = left alone — times the lens on / off."""
+    return [dict(render_arith=a, mlp_f16=f, lens=l) for a, f in ((0, 0), (0, 1), (1, None), (2, None)) for l in (1, 0)]
+
+
+def compare_frames(got, ref):
+    """uint8 frames [n, h, w, 3] against the reference's: worst / mean PSNR over the frames and the share of pixels (any channel) off
+    by more than one LSB."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    if got.shape != ref.shape:
+        raise ValueError(f"render {got.shape} vs png {ref.shape}: pass --resolution")
+    diff = np.abs(got.astype(np.int32) - ref.astype(np.int32))
+    mse = (diff.astype(np.float64) ** 2).reshape(len(diff), -1).mean(1)
+    psnr = np.where(mse == 0, 99.0, 10 * np.log10(255.0 ** 2 / np.maximum(mse, 1e-300)))
+    return {"psnr_db_min": float(psnr.min()), "psnr_db_mean": float(psnr.mean()), "share_off_by_more_than_1": float((diff.max(-1) > 1).mean()),
+            "max_abs_diff": int(diff.max())}
+
+
+def rank_forks(render, reference, combinations=None):
+    """render(combination) -> frames for every combination, compared with `reference`; rows sorted by the share of pixels off by more
+    than one LSB, ties by the mean PSNR (higher first), then by the order of enumeration.  "tied": every combination that is
+    indistinguishable from the closest one on both."""
+    rows = []
+    for i, c in enumerate(fork_combinations() if combinations is None else combinations):
+        rows.append(dict(c, order=i, **compare_frames(render(c), reference)))
+    rows.sort(key=lambda r: (r["share_off_by_more_than_1"], -r["psnr_db_mean"], r["order"]))
+    key = lambda r: (r["share_off_by_more_than_1"], r["psnr_db_mean"])
+    names = ("render_arith", "mlp_f16", "lens")
+    return {"table": rows, "closest": {k: rows[0][k] for k in names}, "tied": [{k: r[k] for k in names} for r in rows if key(r) == key(rows[0])]}
+
+
+def search_forks(options, keys, render, reference, combinations=None, restore=()):
+    """rank_forks with every option in `keys` read first and put back afterwards — also when a render raises; `restore`: further
+    callables run on the way out (the Testbeds' lens switches)."""
+    was = {k: options.get_option(k) for k in keys}
+    try:
+        return rank_forks(render, reference, combinations)
+    finally:
+        for k, v in was.items():
+            options.set_option(k, v)
+        for f in restore:
+            f()
+
+
+def format_fork_table(result):
+    lines = ["render_arith  mlp_f16  lens   off by > 1 LSB   PSNR min / mean (dB)"]
+    for r in result["table"]:
+        lines.append(f"{r['render_arith']:>12}  {'-' if r['mlp_f16'] is None else r['mlp_f16']:>7}  {'on' if r['lens'] else 'off':>4}   "
+                     f"{r['share_off_by_more_than_1']:>13.4%}   {r['psnr_db_min']:.2f} / {r['psnr_db_mean']:.2f}")
+    c = result["closest"]
+    lines.append(f"closest: render_arith {c['render_arith']}, mlp_f16 {'-' if c['mlp_f16'] is None else c['mlp_f16']}, lens {'on' if c['lens'] else 'off'}"
+                 + (f"  ({len(result['tied'])} combinations tied)" if len(result["tied"]) > 1 else ""))
+    return "\n".join(lines)
+
+
+def sampled_poses(args, old_scores, pose_batch):
+    """(c) and (e): render size, the evenly spaced sample of the valid poses (--max-frames), and camera / poses in NGP convention."""
+    from dream2real_amd import accio2ngp
+    W, H = (int(x) for x in args.resolution.split(","))
+    valid = np.nonzero(old_scores)[0]
+    pick = np.arange(len(valid)) if not args.max_frames or args.max_frames >= len(valid) else \
+        np.unique(np.linspace(0, len(valid) - 1, args.max_frames).astype(int))
+    cam = accio2ngp.converter(np.loadtxt(args.cam_pose).reshape(1, 4, 4).astype(np.float32))
+    poses = accio2ngp.converter(pose_batch[valid[pick]].reshape(-1, 4, 4).astype(np.float32))
+    return W, H, pick, cam, poses
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--method-out", required=True, help="method_out/<scene>/ of a reference run")
@@ -105,6 +183,7 @@ def main():
     ap.add_argument("--max-frames", type=int, default=0, help="(c): render at most this many poses, evenly spaced (0 = all)")
     ap.add_argument("--score-tol", type=float, default=1e-3, help="(b): bar on |score - reference| / |reference| (1e-3 cosine -> ~2e-3 on the ratio)")
     ap.add_argument("--psnr-min", type=float, default=40.0, help="(c): bar on the worst frame's PSNR in dB")
+    ap.add_argument("--search-forks", action="store_true", help="(e): render (c)'s poses under every combination of render_arith / mlp_f16 / lens and rank them against the PNGs")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--no-gpu", action="store_true", help="host-only sections")
     ap.add_argument("--out", default=None)
@@ -145,6 +224,7 @@ def main():
                     sec[k]["gpu_loader"] = {"ok": True, "training_views": len(tb.training_views), "dataset_scale": tb.dataset_scale,
                                             "dataset_offset": list(tb.dataset_offset), "background_color": list(tb.background_color)}
                     sec[k]["_tb"] = tb
+                    sec[k]["_lens"] = (tb.nerf.render_with_lens_distortion, tb.nerf.render_lens)      # as loaded, before any section moves the view
                 except Exception as e:          # noqa: BLE001
                     sec[k]["gpu_loader"] = {"ok": False, "error": str(e)}
                     ok = False
@@ -220,17 +300,12 @@ def main():
     else:
         import types
         import torch
-        from dream2real_amd import accio2ngp, combined_rendering
-        W, H = (int(x) for x in args.resolution.split(","))
-        valid = np.nonzero(old_scores)[0]
-        pick = np.arange(len(valid)) if not args.max_frames or args.max_frames >= len(valid) else \
-            np.unique(np.linspace(0, len(valid) - 1, args.max_frames).astype(int))
+        from dream2real_amd import combined_rendering
+        W, H, pick, cam, poses = sampled_poses(args, old_scores, pose_batch)
         task = types.SimpleNamespace(movable_obj=types.SimpleNamespace(vis_model=fg_tb, pose=torch.tensor(np.loadtxt(args.obj_pose), dtype=torch.float32)),
                                      task_bground_obj=types.SimpleNamespace(vis_model=bg_tb))
         tmp = os.path.join(d, "_validate_tmp")
         rend = combined_rendering.renderer(tmp, task, resolution=(W, H))
-        cam = accio2ngp.converter(np.loadtxt(args.cam_pose).reshape(1, 4, 4).astype(np.float32))
-        poses = accio2ngp.converter(pose_batch[valid[pick]].reshape(-1, 4, 4).astype(np.float32))
         got = rend.render(poses, cam, [args.view_idx], None, None, save=False)
         psnr, hist = [], np.zeros(256, np.int64)
         for g, i in zip(got, pick):
@@ -255,6 +330,49 @@ def main():
         import shutil
         shutil.rmtree(tmp, ignore_errors=True)
 
+    # ---------------- (e) which combination of the believed forks renders closest to the cached PNGs
+    if args.search_forks:
+        if need:
+            report["sections"]["e_forks"] = {"skipped": "needs " + ", ".join(need)}
+        else:
+            import torch  # noqa: F401
+            from dream2real_amd import accio2ngp
+            W, H, pick, cam, poses = sampled_poses(args, old_scores, pose_batch)
+            cam = cam[0]
+            T_WO_1 = accio2ngp.converter(np.loadtxt(args.obj_pose).reshape(1, 4, 4).astype(np.float32))[0]
+
+            def render(c):
+                # renderer._setup_view + render_composite with the combination's options (reference combined_rendering.py:95-130)
+                gpu.set_option("render_arith", c["render_arith"])
+                if c["mlp_f16"] is not None:
+                    gpu.set_option("mlp_f16", c["mlp_f16"])
+                for tb in (bg_tb, fg_tb):
+                    tb.set_camera_to_training_view(args.view_idx)
+                    tb.nerf.render_with_lens_distortion = bool(c["lens"])
+                bg_tb.background_color = [0.0, 0.0, 0.0, 1.0]
+                bg_tb.set_nerf_camera_matrix(cam[:-1, :])
+                bg_tb.render_ground_truth = False
+                bg_rgba, bg_depth = bg_tb.render_batch(cam[None, :3, :], W, H)
+                view = fg_tb.view(W, H)
+                gpu.set_background(view, bg_rgba[0], bg_depth[0])
+                return fg_tb.render_composite(view, T_WO_1, cam, poses)
+
+            lens_was = [(report["sections"]["a_snapshots"][k]["_tb"], *report["sections"]["a_snapshots"][k]["_lens"]) for k in ("bg", "fg")]
+
+            def lens_back():
+                for tb, on, lens in lens_was:
+                    tb.nerf.render_with_lens_distortion, tb.nerf.render_lens = on, lens
+
+            try:
+                res = search_forks(gpu, ("render_arith", "mlp_f16"), render, np.stack([frames[i] for i in pick]), restore=(lens_back,))
+                res["frames_compared"] = int(len(pick))
+                print(format_fork_table(res), file=sys.stderr)
+                report["sections"]["e_forks"] = res
+            except ValueError as e:
+                report["sections"]["e_forks"] = {"problem": str(e)}
+                ok = False
+            ran += 1
+
     # ---------------- (d) argmax identity
     if new_scores is None or pose_batch is None or not os.path.exists(goal_path):
         report["sections"]["d_argmax"] = {"skipped": "needs section (b), pose_batch.txt and goal_pose.txt"}
@@ -274,6 +392,7 @@ def main():
 
     for k in ("fg", "bg"):
         report["sections"]["a_snapshots"].get(k, {}).pop("_tb", None)
+        report["sections"]["a_snapshots"].get(k, {}).pop("_lens", None)
     report["ok"] = bool(ok and ran > 0)
     text = json.dumps(report, indent=1)
     print(text)
