@@ -22,6 +22,7 @@ EXPORTS = [
     "d2r_rectify_background_depth", "d2r_ingp_inspect", "d2r_render_score_host", "d2r_png_write", "d2r_png_write_batch",
     "d2r_png_read_batch", "d2r_png_size", "d2r_savetxt", "d2r_ingp_validate", "d2r_debug_gemm_fp8", "d2r_ctx_get_option", "d2r_png_write_batch_bg",
     "d2r_pcd_create", "d2r_pcd_destroy", "d2r_pcd_render", "d2r_pcd_render_score_host",
+    "d2r_tsdf_create", "d2r_tsdf_destroy", "d2r_tsdf_integrate", "d2r_tsdf_read_voxels", "d2r_tsdf_extract", "d2r_obj_write",
 ]
 
 
@@ -128,6 +129,7 @@ def load() -> C.CDLL:
     lib.d2r_text_destroy.restype = None
     lib.d2r_phys_destroy.restype = None
     lib.d2r_pcd_destroy.restype = None
+    lib.d2r_tsdf_destroy.restype = None
     for name in EXPORTS:
         getattr(lib, name)          # every declared symbol must be exported
     if lib.d2r_abi_version() != ABI_VERSION:
@@ -204,6 +206,16 @@ def savetxt(path: str, array):
     a = np.ascontiguousarray(a, np.float64)
     rows, cols = (a.shape[0], 1) if a.ndim == 1 else a.shape
     check(load().d2r_savetxt(os.fsencode(path), ptr(a), C.c_uint64(rows), C.c_uint64(cols), C.c_int(0)))
+
+
+def obj_write(path: str, vertices, triangles, keep=None):
+    """d2r_obj_write: float32 [nv,3] vertices and uint32 [nt,3] triangles -> a Wavefront .obj of `v` and `f` lines (faces
+    with keep[t] == 0 are left out, their vertices stay).  Host only."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
+    assert k is None or k.shape[0] == t.shape[0]
+    check(load().d2r_obj_write(os.fsencode(path), ptr(v), C.c_uint32(v.shape[0]), ptr(t), C.c_uint32(t.shape[0]), ptr(k)))
 
 
 def ingp_validate(data: bytes) -> IngpInfo:

@@ -10,7 +10,7 @@ engine.Context) stands where the reference passes `pyb_planner`.
 
 Shapes come from where the reference takes them: every object's `phys_model` is the path of a Wavefront .obj mesh in
 world coordinates (reference :238 `createCollisionShape(GEOM_MESH, fileName=obj.phys_model)`; written by
-get_phys_models :25-229 — TSDF / Poisson / VHACD, outside the path).  PyBullet turns each shape of the file (an `o` /
+get_phys_models :25-229; its TSDF branch is `get_phys_models` below, Poisson and VHACD stay outside the path).  PyBullet turns each shape of the file (an `o` /
 `g` group: VHACD writes one per convex part) into the convex hull of its vertices, so an object is a compound of
 convex parts: `hulls_from_obj` reads exactly that.  Objects may instead carry vertex arrays (`phys_hull` /
 `phys_hulls`), which take precedence — tests and callers without mesh files use them.
@@ -18,6 +18,7 @@ convex parts: `hulls_from_obj` reads exactly that.  Objects may instead carry ve
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -198,3 +199,155 @@ def create_unsupcol_check(ctx, task_model, sample_res, embodied, unsup_thresh=0.
 
     unsupcol_check.shapes = shapes
     return unsupcol_check, static_objs, [mov]
+
+
+# ------------------------------------------------------------------------------------- physics meshes from RGB-D (TSDF)
+
+TSDF_VOXEL = 0.002                # reference vision_3d/physics_utils.py:62
+TSDF_TRUNC_MULTIPLIER = 8         # Open3D's trunc_voxel_multiplier default (believed)
+TSDF_WEIGHT_THRESHOLD = 3.0       # Open3D's extract_triangle_mesh default (believed)
+TSDF_CLUSTER_KEEP = 0.02          # :107
+ERODE_BACKGROUND, ERODE_OBJECT = 20, 8      # :77-80
+
+
+class TsdfVolume:
+    """d2r_tsdf: a dense (tsdf, weight) grid over `bounds` ([2][3] min, max) on the GPU; frames are integrated in call
+    order, `extract` runs the marching cubes and the clean-up of DESIGN.md section 2c."""
+
+    def __init__(self, ctx, bounds, voxel: float = TSDF_VOXEL, trunc: float | None = None):
+        self.ctx = ctx
+        self.voxel = np.float32(voxel)
+        self.trunc = np.float32(TSDF_TRUNC_MULTIPLIER) * self.voxel if trunc is None else np.float32(trunc)
+        b = np.ascontiguousarray(np.asarray(_np(bounds), np.float64).reshape(6), np.float32)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.d2r_tsdf_create(ctx.h, _lib.ptr(b), C.c_float(self.voxel), C.c_float(self.trunc), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.d2r_tsdf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def integrate(self, depth_u16, mask, intrinsics, cam_pose, erode_k: int):
+        d = np.ascontiguousarray(depth_u16, np.uint16)
+        m = np.ascontiguousarray(mask, np.uint8)
+        assert d.ndim == 2 and m.shape == d.shape
+        K = np.ascontiguousarray(np.asarray(_np(intrinsics), np.float64).reshape(9), np.float32)
+        T = np.ascontiguousarray(np.asarray(_np(cam_pose), np.float64).reshape(16), np.float32)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_integrate(self.h, _lib.ptr(d), _lib.ptr(m), C.c_uint32(d.shape[1]), C.c_uint32(d.shape[0]),
+                                                       _lib.ptr(K), _lib.ptr(T), C.c_uint32(int(erode_k))))
+
+    def read_voxels(self):
+        """-> (block coordinates int32 [n,3] (x, y, z), tsdf float32 [n,16,16,16] indexed [z][y][x], weight likewise), the
+        blocks any frame touched in (z, y, x) order."""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_read_voxels(self.h, C.byref(n), None, None, None))
+        coords = np.zeros((n.value, 3), np.int32)
+        tsdf = np.zeros((n.value, 16, 16, 16), np.float32)
+        weight = np.zeros((n.value, 16, 16, 16), np.float32)
+        if n.value:
+            self.ctx.check(self.ctx.lib.d2r_tsdf_read_voxels(self.h, C.byref(n), _lib.ptr(coords), _lib.ptr(tsdf), _lib.ptr(weight)))
+        return coords, tsdf, weight
+
+    def extract(self, weight_threshold: float = TSDF_WEIGHT_THRESHOLD, crop=None, cluster_keep: float = TSDF_CLUSTER_KEEP) -> dict:
+        """-> vertices float32 [nv,3], triangles uint32 [nt,3] (all that survive the crop), clusters int32 [nt], keep bool
+        [nt] (False: in a cluster below cluster_keep of the largest), centre float64 [3]."""
+        c = None if crop is None else np.ascontiguousarray(np.asarray(_np(crop), np.float64).reshape(6), np.float32)
+        nv, nt = C.c_uint32(0), C.c_uint32(0)
+        args = (self.h, C.c_float(weight_threshold), _lib.ptr(c), C.c_double(cluster_keep), C.byref(nv), C.byref(nt))
+        self.ctx.check(self.ctx.lib.d2r_tsdf_extract(*args, None, None, None, None, None))
+        v = np.zeros((nv.value, 3), np.float32)
+        t = np.zeros((nt.value, 3), np.uint32)
+        lab = np.zeros(nt.value, np.int32)
+        keep = np.zeros(nt.value, np.uint8)
+        centre = np.zeros(3, np.float64)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_extract(*args, _lib.ptr(v), _lib.ptr(t), _lib.ptr(lab), _lib.ptr(keep), _lib.ptr(centre)))
+        return dict(vertices=v, triangles=t, clusters=lab, keep=keep.astype(bool), centre=centre)
+
+
+def vhacd_convexify(concave_path: str, convex_path: str, obj_id: int):
+    """The reference's VHACD call (:185-193) through PyBullet, when PyBullet is installed.  Nothing is downloaded."""
+    try:
+        import pybullet as p
+    except ImportError as e:
+        raise RuntimeError("get_phys_models: mesh_{id}.obj comes from VHACD, which needs PyBullet (pybullet.vhacd), and PyBullet is "
+                           "not importable here; install it, or pass convexify=callable(concave_path, convex_path, obj_id)") from e
+    log = os.path.join(os.path.dirname(convex_path), f"mesh_vhacd_{obj_id}.log")
+    p.vhacd(concave_path, convex_path, log, resolution=1000000 if obj_id == 0 else 10000, depth=80, concavity=0.00002, gamma=0.00002,
+            minVolumePerCH=0.00002, maxNumVerticesPerCH=64)
+
+
+def get_phys_models(depths, cam_poses, intrinsics, masks, num_objs, scene_bounds, embodied=False, save_dir=None, vis=False,
+                    use_cache=True, use_phys_tsdf=False, use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None):
+    """reference vision_3d/physics_utils.py:25-229 -> (mesh_paths, init_poses): per object id the path of mesh_{id}.obj and
+    its initial pose (float32 4x4 tensor: identity with the mesh centre as translation).
+
+    use_cache: read <save_dir>/mesh_{id}.obj and init_pose_{id}.txt (:28-50).  Otherwise, with use_phys_tsdf, fuse the masked
+    frames on the GPU, write mesh_concave_{id}.obj and init_pose_{id}.txt, and hand the concave mesh
+    to `convexify(concave_path, convex_path, obj_id)` (default: PyBullet's VHACD with the reference's arguments).  The
+    Poisson branch (use_phys_tsdf=False) is not built.  `vis` (an Open3D window) and `embodied` (PyBullet's connection)
+    are accepted and ignored.  `ctx`: an engine.Context (default: a fresh one on device 0)."""
+    import torch
+    if use_cache:
+        mesh_paths, init_poses = [], []
+        for obj_id in range(num_objs):
+            mesh_paths.append(os.path.join(save_dir, f"mesh_{obj_id}.obj"))
+            init_poses.append(torch.tensor(np.loadtxt(f"{save_dir}/init_pose_{obj_id}.txt")).float())
+        return mesh_paths, init_poses
+    if not use_phys_tsdf:
+        raise NotImplementedError("get_phys_models: the Poisson branch (use_phys_tsdf=False: per-frame point clouds, statistical outlier "
+                                  "removal, Poisson reconstruction) is not implemented; set use_phys_tsdf=True")
+    if save_dir is None:
+        raise ValueError("get_phys_models: save_dir is needed, the result is the paths of the mesh files")
+    os.makedirs(save_dir, exist_ok=True)
+    convexify = convexify or vhacd_convexify
+    own_ctx = ctx is None
+    if own_ctx:
+        from . import engine
+        ctx = engine.Context(0)
+    bounds = np.asarray(_np(scene_bounds), np.float64).reshape(2, 3)
+    frame_range = [single_view_idx] * 4 if use_vis_pcds else range(len(depths))
+    mesh_paths, init_poses = [], []
+    try:
+        for obj_id in range(num_objs):
+            vol = TsdfVolume(ctx, bounds)
+            try:
+                for f in frame_range:
+                    depth = _np(depths[f])
+                    u16 = (depth * 1000).astype(np.uint16)                      # the reference's expression, in the array's own type (:88)
+                    vol.integrate(u16, _np(masks[f]) == obj_id, intrinsics, cam_poses[f], ERODE_BACKGROUND if obj_id == 0 else ERODE_OBJECT)
+                try:
+                    mesh = vol.extract(TSDF_WEIGHT_THRESHOLD, bounds, TSDF_CLUSTER_KEEP)
+                except _lib.D2RError as e:
+                    raise ValueError(f"get_phys_models: object {obj_id} has no TSDF surface inside scene_bounds ({e})") from e
+            finally:
+                vol.close()
+            init_pose = torch.eye(4)
+            init_pose[:3, 3] = torch.tensor(mesh["centre"])
+            init_poses.append(init_pose)
+            _lib.savetxt(os.path.join(save_dir, f"init_pose_{obj_id}.txt"), init_pose.numpy())
+            concave = os.path.join(save_dir, f"mesh_concave_{obj_id}.obj")
+            _lib.obj_write(concave, mesh["vertices"], mesh["triangles"], mesh["keep"])
+            convex = os.path.join(save_dir, f"mesh_{obj_id}.obj")
+            convexify(concave, convex, obj_id)
+            mesh_paths.append(convex)
+    finally:
+        if own_ctx:
+            ctx.close()
+    return mesh_paths, init_poses
+
+
+def create_lazy_phys_mods(scene_model, movable_obj, scene_bounds, save_dir, embodied=False, vis=False, use_cache=False, use_phys_tsdf=True,
+                          use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None):
+    """reference scene_model.py:116-125 (TaskModel.create_lazy_phys_mods): two physics models, the movable object (mask 1)
+    and everything else (mask 0) -> ([bground_phys, movable_phys], [bground_init_pose, movable_init_pose])."""
+    fg_bg_masks = [(_np(m) == movable_obj.mask_idx).astype(np.uint8) for m in scene_model.masks]
+    return get_phys_models(scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, fg_bg_masks, num_objs=2,
+                           scene_bounds=scene_bounds, embodied=embodied, save_dir=save_dir, vis=vis, use_cache=use_cache,
+                           use_phys_tsdf=use_phys_tsdf, use_vis_pcds=use_vis_pcds, single_view_idx=single_view_idx, ctx=ctx, convexify=convexify)

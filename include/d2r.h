@@ -641,6 +641,59 @@ D2R_API int d2r_pcd_render_score_host(d2r_ctx *ctx, const d2r_pcd *bg, const d2r
                                       const float *obj_poses, uint32_t K, const float *text_embeds, uint32_t C,
                                       float logit_scale, float *logits_out, uint8_t *frames_out);
 
+/* ------------------------------------------------- TSDF fusion of RGB-D frames into a triangle mesh (use_phys_tsdf)
+ *
+ * replaces the TSDF branch of reference vision_3d/physics_utils.py:58-115 (get_phys_models: Open3D VoxelBlockGrid on the
+ * CPU, extract_triangle_mesh, crop, cluster removal, centre).  The rule is DESIGN.md section 2c; Open3D's defaults in it are
+ * believed, not checked against Open3D.  State is a DENSE grid of (tsdf, weight) fp32 pairs over the bounds padded by
+ * `trunc` and rounded out to whole blocks of 16^3 voxels; voxel g sits at g * voxel on every axis.
+ */
+typedef struct d2r_tsdf d2r_tsdf;
+
+/* bounds: host [6] min xyz, max xyz.  voxel 0.002 and trunc 0.016 in the reference.  A volume of more than 2^31 voxels
+ * (16 GiB of state) is refused with D2R_ERR_UNSUPPORTED and a message that starts "TSDF volume over the cap". */
+D2R_API int d2r_tsdf_create(d2r_ctx *ctx, const float *bounds, float voxel, float trunc, d2r_tsdf **out);
+D2R_API void d2r_tsdf_destroy(d2r_tsdf *vol);
+
+/*
+ * One frame, in call order.  depth_u16 host [h][w] millimetres, mask_u8 host [h][w] (non-zero = the object), intrinsics
+ * host [9] row-major 3x3, cam_pose host [16] row-major camera-to-world, erode_k 1 .. 32 (1 = no erosion).
+ * The mask is eroded by an erode_k x erode_k rectangle anchored at (k/2, k/2) (outside the frame counts as set); a pixel is
+ * valid when it survives and 0 < z = u16 / 1000 <= 3.  Blocks a valid pixel's ray crosses for depths z - trunc .. z + trunc
+ * in voxel steps are the frame's blocks; their voxels take tsdf = (w tsdf + t) / (w + 1), w += 1 with
+ * t = min((z_pixel - z_cam) / trunc, 1) where the voxel projects (rounded to nearest) onto a valid pixel, z_cam > 0 and
+ * z_pixel - z_cam >= -trunc.  A frame without a valid pixel changes nothing.  Synchronous.
+ */
+D2R_API int d2r_tsdf_integrate(d2r_tsdf *vol, const uint16_t *depth_u16, const uint8_t *mask_u8, uint32_t w, uint32_t h,
+                               const float *intrinsics, const float *cam_pose, uint32_t erode_k);
+
+/*
+ * Parity hook: the blocks any frame touched, in (z, y, x) order.  *n_blocks holds the capacity of the buffers on entry and
+ * the count on return; with all three buffers NULL only the count is returned.  block_coords host [n][3] (x, y, z of the
+ * block, voxel 16 b .. 16 b + 15), tsdf / weight host [n][16][16][16] indexed [z][y][x].
+ */
+D2R_API int d2r_tsdf_read_voxels(d2r_tsdf *vol, uint32_t *n_blocks, int32_t *block_coords, float *tsdf, float *weight);
+
+/*
+ * Marching cubes over cubes whose eight corners all have weight >= weight_threshold (3 in the reference's setting), one
+ * vertex per crossed edge at p0 + ((p1 - p0) t0) / (t0 - t1), vertices ordered by (z, y, x of the edge's lower voxel, axis),
+ * triangles by (cube z, y, x, table order); then on the host the inclusive crop (host [6], NULL = none; a triangle survives
+ * when its three vertices do, unreferenced vertices are dropped), clusters of triangles that share vertices, and
+ * keep[t] = 0 for triangles of clusters smaller than cluster_keep (0.02) times the largest.  centre = mean of the vertex
+ * array in fp64.  *n_vertices / *n_triangles: capacities on entry, counts on return; call once with every buffer NULL for
+ * the counts, then again to fill (the result is kept in between).  vertices host [nv][3], triangles host [nt][3],
+ * clusters host [nt], keep host [nt], centre host [3]; each may be NULL.  A volume without a surface is D2R_ERR_INVALID
+ * ("seen in no frame").  Synchronous.
+ */
+D2R_API int d2r_tsdf_extract(d2r_tsdf *vol, float weight_threshold, const float *crop, double cluster_keep, uint32_t *n_vertices,
+                             uint32_t *n_triangles, float *vertices, uint32_t *triangles, int32_t *clusters, uint8_t *keep,
+                             double *centre);
+
+/* mesh_concave_{id}.obj: "v %f %f %f" per vertex, "f a b c" (1-based) per triangle with keep[t] != 0 (keep NULL = all).
+ * Vertices of dropped triangles stay in the file, as Open3D's remove_triangles_by_mask leaves them.  Host only. */
+D2R_API int d2r_obj_write(const char *path, const float *vertices, uint32_t n_vertices, const uint32_t *triangles,
+                          uint32_t n_triangles, const uint8_t *keep);
+
 #ifdef __cplusplus
 }
 #endif
