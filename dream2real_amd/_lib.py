@@ -23,6 +23,8 @@ EXPORTS = [
     "d2r_png_read_batch", "d2r_png_size", "d2r_savetxt", "d2r_ingp_validate", "d2r_debug_gemm_fp8", "d2r_ctx_get_option", "d2r_png_write_batch_bg",
     "d2r_pcd_create", "d2r_pcd_destroy", "d2r_pcd_render", "d2r_pcd_render_score_host",
     "d2r_tsdf_create", "d2r_tsdf_destroy", "d2r_tsdf_integrate", "d2r_tsdf_read_voxels", "d2r_tsdf_extract", "d2r_obj_write",
+    "d2r_png_write_channels", "d2r_png_info", "d2r_png_read_grey", "d2r_png_read_rgb",
+    "d2r_scene_bound_masks", "d2r_masks_prune", "d2r_masks_components", "d2r_masks_lut", "d2r_masks_get_timing",
 ]
 
 
@@ -176,6 +178,40 @@ def png_write_batch_bg(frames, background, out_dir: str, first_index: int = 0, t
                                         os.fsencode(out_dir), C.c_uint32(first_index), C.c_int(threads)))
 
 
+def png_write_channels(pixels, path: str, level: int = -1):
+    """d2r_png_write_channels: uint8 [h,w] (grey), [h,w,3] (RGB) or [h,w,4] (RGBA) -> a PNG file (host only)."""
+    a = np.ascontiguousarray(pixels, np.uint8)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
+        raise ValueError(f"expected [h,w], [h,w,3] or [h,w,4], got shape {a.shape}")
+    check(load().d2r_png_write_channels(ptr(a), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]), C.c_uint32(a.shape[2]), os.fsencode(path),
+                                        C.c_int(level)))
+
+
+def png_info(path: str):
+    """d2r_png_info -> (w, h, channels, bits)."""
+    v = [C.c_uint32(0) for _ in range(4)]
+    check(load().d2r_png_info(os.fsencode(path), *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+def png_read_rgb(path: str, size=None) -> np.ndarray:
+    """d2r_png_read_rgb: one 8-bit PNG -> uint8 [h,w,3] in R, G, B order (grey replicated, alpha dropped)."""
+    w, h = size or png_info(path)[:2]
+    out = np.empty((h, w, 3), np.uint8)
+    check(load().d2r_png_read_rgb(os.fsencode(path), C.c_uint32(w), C.c_uint32(h), ptr(out)))
+    return out
+
+
+def png_read_grey(path: str, bits: int = 8, size=None) -> np.ndarray:
+    """d2r_png_read_grey: a grey PNG of `bits` (8 or 16) -> uint8 / uint16 [h,w].  `size` = (w, h) expected, default the file's."""
+    w, h = size or png_info(path)[:2]
+    out = np.empty((h, w), np.uint16 if bits == 16 else np.uint8)
+    check(load().d2r_png_read_grey(os.fsencode(path), C.c_uint32(bits), C.c_uint32(w), C.c_uint32(h), ptr(out)))
+    return out
+
+
 def png_size(path: str):
     w, h = C.c_uint32(0), C.c_uint32(0)
     check(load().d2r_png_size(os.fsencode(path), C.byref(w), C.byref(h)))
@@ -216,6 +252,94 @@ def obj_write(path: str, vertices, triangles, keep=None):
     k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
     assert k is None or k.shape[0] == t.shape[0]
     check(load().d2r_obj_write(os.fsencode(path), ptr(v), C.c_uint32(v.shape[0]), ptr(t), C.c_uint32(t.shape[0]), ptr(k)))
+
+
+def _h(ctx) -> C.c_void_p:
+    """The d2r_ctx pointer of an engine.Context (or a raw handle)."""
+    h = getattr(ctx, "h", ctx)
+    return h if isinstance(h, C.c_void_p) else C.c_void_p(h)
+
+
+def _frames(a, dtype, name):
+    a = np.ascontiguousarray(a, dtype)
+    if a.ndim != 3:
+        raise ValueError(f"{name} must be [n, h, w], got shape {a.shape}")
+    return a
+
+
+def scene_bound_masks(ctx, depth_u16, poses, K, bounds, window: int = 50, return_raw: bool = False):
+    """d2r_scene_bound_masks: uint16 millimetre depth [n,h,w], float32 poses [n,4,4], K [3,3], bounds [[min xyz],[max xyz]] ->
+    uint8 0 / 255 [n,h,w]; with return_raw also the mask before the closing.  ctx: a d2r_ctx pointer."""
+    d = _frames(depth_u16, np.uint16, "depth_u16")
+    n, h, w = d.shape
+    T = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+    if T.shape[0] != n:
+        raise ValueError(f"{T.shape[0]} poses for {n} frames")
+    Kd = np.ascontiguousarray(K, np.float64).reshape(9)
+    b = np.array(bounds, np.float64).reshape(6)          # a copy: the caller's bounds stay as they are
+    out = np.empty((n, h, w), np.uint8)
+    raw = np.empty((n, h, w), np.uint8) if return_raw else None
+    check(load().d2r_scene_bound_masks(_h(ctx), ptr(d), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(T), ptr(Kd), ptr(b),
+                                       C.c_uint32(window), ptr(out), ptr(raw)), _h(ctx))
+    return (out, raw) if return_raw else out
+
+
+def masks_prune(ctx, mode: int, masks, depth_u16=None, oob=None, poses=None, K=None, centre=None, min_area: int = 200):
+    """d2r_masks_prune: mode 0 duplicate_prune (needs depth_u16, poses, K, centre), 1 disconnected_prune; uint8 labels [n,h,w] ->
+    pruned uint8 labels with 255 where oob == 255."""
+    m = _frames(masks, np.uint8, "masks")
+    n, h, w = m.shape
+    d = None if depth_u16 is None else _frames(depth_u16, np.uint16, "depth_u16")
+    o = None if oob is None else _frames(oob, np.uint8, "oob")
+    for a in (d, o):
+        if a is not None and a.shape != m.shape:
+            raise ValueError(f"shape {a.shape} does not match the masks' {m.shape}")
+    T = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+    if T is not None and T.shape[0] != n:
+        raise ValueError(f"{T.shape[0]} poses for {n} frames")
+    Kd = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)
+    c = None if centre is None else np.ascontiguousarray(centre, np.float64).reshape(3)
+    out = np.empty((n, h, w), np.uint8)
+    check(load().d2r_masks_prune(_h(ctx), C.c_int(mode), ptr(m), ptr(d), ptr(o), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(T),
+                                 ptr(Kd), ptr(c), C.c_uint32(min_area), ptr(out)), _h(ctx))
+    return out
+
+
+def masks_components(ctx, mask, depth_u16):
+    """d2r_masks_components (parity hook, one frame [h,w]) -> (order-key image uint32 [h,w], area uint32 [h,w], sums uint64 [h,w,4])."""
+    m = np.ascontiguousarray(mask, np.uint8)
+    d = np.ascontiguousarray(depth_u16, np.uint16)
+    if m.ndim != 2 or d.shape != m.shape:
+        raise ValueError("mask and depth_u16 must be [h, w] of one shape")
+    h, w = m.shape
+    keys, area, sums = np.empty((h, w), np.uint32), np.empty((h, w), np.uint32), np.empty((h, w, 4), np.uint64)
+    check(load().d2r_masks_components(_h(ctx), ptr(m), ptr(d), C.c_uint32(w), C.c_uint32(h), ptr(keys), ptr(area), ptr(sums)),
+          _h(ctx))
+    return keys, area, sums
+
+
+def masks_lut(ctx, masks, lut, oob=None, alpha: bool = False):
+    """d2r_masks_lut: (lut[masks] != 0) | (oob != 0) as uint8 0 / 1 [n,h,w]; with alpha also 255 (1 - out)."""
+    m = _frames(masks, np.uint8, "masks")
+    n, h, w = m.shape
+    o = None if oob is None else _frames(oob, np.uint8, "oob")
+    if o is not None and o.shape != m.shape:
+        raise ValueError(f"shape {o.shape} does not match the masks' {m.shape}")
+    t = np.ascontiguousarray(lut, np.uint8).reshape(-1)
+    if t.shape[0] != 256:
+        raise ValueError("lut must have 256 entries")
+    out = np.empty((n, h, w), np.uint8)
+    al = np.empty((n, h, w), np.uint8) if alpha else None
+    check(load().d2r_masks_lut(_h(ctx), ptr(m), ptr(o), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(t), ptr(out), ptr(al)),
+          _h(ctx))
+    return (out, al) if alpha else out
+
+
+def masks_timing(ctx):
+    """d2r_masks_get_timing -> (upload, kernels, download) of the context's last batch mask call, device-event milliseconds."""
+    ms = np.zeros(3, np.float64)
+    check(load().d2r_masks_get_timing(_h(ctx), ptr(ms)), _h(ctx))
+    return tuple(float(x) for x in ms)
 
 
 def ingp_validate(data: bytes) -> IngpInfo:

@@ -310,7 +310,8 @@ void d2r_ctx_destroy(d2r_ctx *c)
     d2r_ctx::Buf *bufs[] = {&c->cams, &c->queue, &c->queue2, &c->sort_counts, &c->counters, &c->frames, &c->rgba, &c->depth, &c->poses,
                             &c->text, &c->logits, &c->pix, &c->bg_rgba, &c->bg_depth, &c->bg_u8, &c->rects, &c->bg_patches, &c->rect_ws, &c->lens_tab,
                             &c->patches2, &c->frames2, &c->bg_l0, &c->l0_a1, &c->l0_q2, &c->l0_misc,
-                            &c->pcd_mats, &c->pcd_bg_keys, &c->pcd_bg_frame, &c->pcd_cols};
+                            &c->pcd_mats, &c->pcd_bg_keys, &c->pcd_bg_frame, &c->pcd_cols,
+                            &c->mask_in, &c->mask_out, &c->mask_ws};
     for (auto *b : bufs)
         if (b->p) hipFree(b->p);
     for (auto &b : c->clipws)
@@ -323,6 +324,8 @@ void d2r_ctx_destroy(d2r_ctx *c)
     hipEvent_t evs[] = {c->ev_fork, c->ev_prep[0], c->ev_prep[1], c->ev_clip[0], c->ev_clip[1], c->ev_march[0], c->ev_march[1],
                         c->ev_copy[0], c->ev_copy[1]};
     for (hipEvent_t e : evs)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->mask_ev)
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; k++)
         if (c->frame_host[k]) (void)hipHostFree(c->frame_host[k]);

@@ -127,6 +127,9 @@ struct d2r_ctx {
     // background of the current view
     Buf bg_rgba, bg_depth, bg_u8;
     Buf pcd_mats, pcd_bg_keys, pcd_bg_frame, pcd_cols;   // pcd.hip: candidate matrices, background key buffer and colour frame, colour table of the current call
+    Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots, result frames, union-find parents + component statistics of a pass
+    hipEvent_t mask_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... upload / kernels / download boundaries of the last batch call (d2r_masks_get_timing)
+    bool mask_timed = false;
     Buf lens_tab;                // undistorted camera-space directions of the current view's pixels (nerf.hip lens_table)
     float lens_key[10] = {};     // ... and the view (size, intrinsics, coefficients) it was computed for
     bool lens_key_valid = false;

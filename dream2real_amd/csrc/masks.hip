@@ -1,0 +1,662 @@
+// masks.hip — the mask geometry in front of build_scene_model: scene-bound masks from depth (reference data_loader.py:71-122,
+// Open3D + two 50 x 50 cv2 morphology passes per frame on the CPU) and the connected-component pruning of label images
+// (reference segmentation/XMem_infer.py:264-351, one cv2.connectedComponents per label per frame).  The rule is DESIGN.md
+// section 2d, restated in numpy by tests/masks_ref.py and held to it bit for bit.
+//   k_scene_bounds   one lane per pixel in fp64, the raw mask bit-packed: 64 pixels per uint64 through __ballot
+//   k_morph          dilation / erosion by a k x k rectangle on the packed words: log2(k) shift-and-OR (AND) steps along a row,
+//                    the same doubling over the rows of an LDS tile of words
+//   k_label_tiles    union-find over raster indices inside a 64 x 16 tile in LDS
+//   k_label_seams    unions across tile borders, lock-free: find both roots, atomicMin the larger root's parent
+//   k_label_flatten  every pixel points at its root = the smallest raster index of its component = the component's order key
+//   k_comp_stats     area and (n, sum d, sum j d, sum i d) at the root's index: integer atomics, equal roots combined per wave
+//   k_select_*       per label: component count, best distance (bit pattern of a non-negative double) or area, tie rule
+//   k_prune_write    the pruned label image with the out-of-scene overwrite
+//   k_mask_lut       out = lut[mask] | (oob != 0), optionally alpha = 255 (1 - out)
+// Every value is written by ordinary vector stores from C++.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "d2r_internal.h"
+
+namespace {
+
+constexpr uint32_t MK_THREADS = 256;
+constexpr int CL_TW = 4, CL_TR = 64, CL_ROWS = 128;      // k_morph: words x output rows of a tile, rows held (CL_TR + 63 <= CL_ROWS)
+constexpr int LB_TW = 64, LB_TH = 16, LB_PX = LB_TW * LB_TH;   // k_label_tiles: tile of the per-tile labelling
+constexpr uint32_t NO_KEY = 0xffffffffu;
+constexpr size_t MK_WS_BUDGET = (size_t)1 << 30;         // labelling workspace per pass of frames (D2R_MASKS_WS_BYTES overrides it)
+
+struct MaskCam {
+    double fx, fy, cx, cy;
+};
+struct MaskBox {
+    double lo[3], hi[3];
+};
+struct MaskCentre {
+    double c[3];
+};
+// per-root statistics: n, sum d, sum j d, sum i d over the pixels with d16 > 0 as uint64, then the area in the low half of word 4
+constexpr int ST_WORDS = 5;
+
+// ------------------------------------------------------------------------------------------------ scene bounds
+
+__global__ __launch_bounds__(MK_THREADS) void k_scene_bounds(const uint16_t *__restrict__ depth, const float *__restrict__ poses, MaskCam c, MaskBox b,
+                                                             int W, int H, int WW, unsigned long long *__restrict__ bits)
+{
+    const uint32_t f = blockIdx.y;
+    const uint32_t word = blockIdx.x * (MK_THREADS / 64) + (threadIdx.x >> 6);      // one wave per word of 64 pixels
+    if (word >= (uint32_t)H * (uint32_t)WW) return;
+    const int i = (int)(word / (uint32_t)WW), w = (int)(word - (uint32_t)i * (uint32_t)WW), lane = (int)(threadIdx.x & 63), j = w * 64 + lane;
+    bool set = false;
+    if (j < W) {
+        const uint16_t d = depth[(size_t)f * W * H + (size_t)i * W + j];
+        const float *T = poses + (size_t)f * 16;
+        const double z = (double)((float)d / 1000.0f);
+        const double x = ((double)j - c.cx) * z / c.fx, y = ((double)i - c.cy) * z / c.fy;
+        const double px = (((double)T[0] * x + (double)T[1] * y) + (double)T[2] * z) + (double)T[3];
+        const double py = (((double)T[4] * x + (double)T[5] * y) + (double)T[6] * z) + (double)T[7];
+        const double pz = (((double)T[8] * x + (double)T[9] * y) + (double)T[10] * z) + (double)T[11];
+        set = d > 0 && pz > -0.40 && (px < b.lo[0] || px > b.hi[0] || py < b.lo[1] || py > b.hi[1] || pz < b.lo[2] || pz > b.hi[2]);
+    }
+    const unsigned long long m = __ballot(set);
+    if (lane == 0) bits[(size_t)f * H * WW + word] = m;
+}
+
+// x (192 bits, x[0] lowest) >>= s with `fill` shifted in at the top, 1 <= s <= 63
+__device__ inline void shr192(const unsigned long long x[3], int s, unsigned long long fill, unsigned long long y[3])
+{
+    y[0] = (x[0] >> s) | (x[1] << (64 - s));
+    y[1] = (x[1] >> s) | (x[2] << (64 - s));
+    y[2] = (x[2] >> s) | (fill << (64 - s));
+}
+
+// dst(i, j) = OR (ERODE: AND) of src(i + a, j + b), a and b in [-k/2, -k/2 + k - 1], positions outside the frame ignored (they read
+// as the operation's identity, the tail bits of a row's last word included).  A workgroup makes CL_TW words x CL_TR rows.
+template <bool ERODE>
+__global__ __launch_bounds__(MK_THREADS) void k_morph(const unsigned long long *__restrict__ src, unsigned long long *__restrict__ dst, int W, int H,
+                                                      int WW, int k)
+{
+    __shared__ unsigned long long buf[2][CL_ROWS][CL_TW];
+    const unsigned long long ident = ERODE ? ~0ull : 0ull;
+    const int t = (int)threadIdx.x, hh = k / 2;
+    const int w0 = (int)blockIdx.x * CL_TW, i0 = (int)blockIdx.y * CL_TR;
+    const unsigned long long *s = src + (size_t)blockIdx.z * H * WW;
+    unsigned long long *o = dst + (size_t)blockIdx.z * H * WW;
+    const unsigned long long tail = (W & 63) ? (~0ull << (W & 63)) : 0ull;      // the bits past the row's end in its last word
+    auto ld = [&](int gi, int w) -> unsigned long long {
+        if (gi < 0 || gi >= H || w < 0 || w >= WW) return ident;
+        unsigned long long v = s[(size_t)gi * WW + w];
+        if (w == WW - 1) v = ERODE ? (v | tail) : (v & ~tail);
+        return v;
+    };
+    auto op = [](unsigned long long a, unsigned long long b) -> unsigned long long { return ERODE ? (a & b) : (a | b); };
+    for (int q = t; q < CL_ROWS * CL_TW; q += (int)MK_THREADS) {
+        const int r = q / CL_TW, cw = q - r * CL_TW, gi = i0 - hh + r, w = w0 + cw;
+        unsigned long long v = ident;
+        if (r < CL_TR + k - 1 && w < WW && gi >= 0 && gi < H) {
+            unsigned long long x[3] = {ld(gi, w - 1), ld(gi, w), ld(gi, w + 1)}, y[3];
+            // x(j) = op over src(j .. j + L - 1), L doubling up to k
+            int L = 1;
+            while (2 * L <= k) {
+                shr192(x, L, ident, y);
+                x[0] = op(x[0], y[0]); x[1] = op(x[1], y[1]); x[2] = op(x[2], y[2]);
+                L *= 2;
+            }
+            if (k > L) {
+                shr192(x, k - L, ident, y);
+                x[0] = op(x[0], y[0]); x[1] = op(x[1], y[1]); x[2] = op(x[2], y[2]);
+            }
+            v = hh ? ((x[1] << hh) | (x[0] >> (64 - hh))) : x[1];       // the window starts k/2 to the left
+        }
+        buf[0][r][cw] = v;
+    }
+    __syncthreads();
+    int cur = 0;
+    auto step = [&](int sft) {
+        for (int q = t; q < CL_ROWS * CL_TW; q += (int)MK_THREADS) {
+            const int r = q / CL_TW, cw = q - r * CL_TW;
+            const unsigned long long a = buf[cur][r][cw], bb = r + sft < CL_ROWS ? buf[cur][r + sft][cw] : ident;
+            buf[cur ^ 1][r][cw] = op(a, bb);
+        }
+        __syncthreads();
+        cur ^= 1;
+    };
+    int L = 1;
+    while (2 * L <= k) {
+        step(L);
+        L *= 2;
+    }
+    if (k > L) step(k - L);
+    for (int q = t; q < CL_TR * CL_TW; q += (int)MK_THREADS) {
+        const int r = q / CL_TW, cw = q - r * CL_TW, gi = i0 + r, w = w0 + cw;
+        if (gi < H && w < WW) {
+            unsigned long long v = buf[cur][r][cw];       // tile row r = frame row gi - k/2: the window's first row
+            if (w == WW - 1) v &= ~tail;
+            o[(size_t)gi * WW + w] = v;
+        }
+    }
+}
+
+// packed bits -> 0 / 255 bytes, eight pixels per lane
+__global__ __launch_bounds__(MK_THREADS) void k_unpack(const unsigned long long *__restrict__ bits, int W, int H, int WW, uint8_t *__restrict__ out)
+{
+    const int W8 = (W + 7) / 8;
+    const uint32_t q = blockIdx.x * MK_THREADS + threadIdx.x;
+    if (q >= (uint32_t)H * (uint32_t)W8) return;
+    const int i = (int)(q / (uint32_t)W8), j0 = (int)(q - (uint32_t)i * (uint32_t)W8) * 8;
+    const unsigned long long word = bits[(size_t)blockIdx.y * H * WW + (size_t)i * WW + (j0 >> 6)];
+    const uint32_t m = (uint32_t)(word >> (j0 & 63)) & 0xffu;
+    uint8_t *dst = out + (size_t)blockIdx.y * W * H + (size_t)i * W + j0;
+    if ((W & 7) == 0) {
+        uint2 v;
+        v.x = ((m & 1u) ? 0xffu : 0u) | ((m & 2u) ? 0xff00u : 0u) | ((m & 4u) ? 0xff0000u : 0u) | ((m & 8u) ? 0xff000000u : 0u);
+        v.y = ((m & 16u) ? 0xffu : 0u) | ((m & 32u) ? 0xff00u : 0u) | ((m & 64u) ? 0xff0000u : 0u) | ((m & 128u) ? 0xff000000u : 0u);
+        *reinterpret_cast<uint2 *>(dst) = v;
+    } else {
+        for (int e = 0; e < 8 && j0 + e < W; ++e) dst[e] = ((m >> e) & 1u) ? 255 : 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ labelling
+
+// Union-find where a link always goes from the larger index to the smaller: a root is the smallest index of its set whatever
+// order the atomics ran in.  `par` is LDS or global memory that other lanes update with atomicMin while it is read.
+template <int SCOPE>
+__device__ inline uint32_t uf_find(uint32_t *par, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, SCOPE);
+        if (p == x) return x;
+        x = p;
+    }
+}
+
+template <int SCOPE>
+__device__ inline void uf_unite(uint32_t *par, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = uf_find<SCOPE>(par, a);
+        b = uf_find<SCOPE>(par, b);
+        if (a == b) return;
+        if (a < b) {
+            const uint32_t s = a;
+            a = b;
+            b = s;
+        }
+        const uint32_t old = atomicMin(&par[a], b);       // a was a root: linked; else a's parent `old` < a still has to meet b
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// parent[g] = raster index of the smallest pixel of g's component INSIDE its tile (label 0: g itself)
+__global__ __launch_bounds__(MK_THREADS) void k_label_tiles(const uint8_t *__restrict__ mask, int W, int H, uint32_t *__restrict__ parent)
+{
+    __shared__ uint8_t lab[LB_PX];
+    __shared__ uint32_t par[LB_PX];
+    const int t = (int)threadIdx.x, j0 = (int)blockIdx.x * LB_TW, i0 = (int)blockIdx.y * LB_TH;
+    const size_t base = (size_t)blockIdx.z * W * H;
+    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
+        const int r = q / LB_TW, c = q - r * LB_TW, i = i0 + r, j = j0 + c;
+        lab[q] = (i < H && j < W) ? mask[base + (size_t)i * W + j] : 0;
+        par[q] = (uint32_t)q;
+    }
+    __syncthreads();
+    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
+        const int r = q / LB_TW, c = q - r * LB_TW;
+        const uint8_t l = lab[q];
+        if (!l) continue;
+        if (c > 0 && lab[q - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - 1));
+        if (r > 0) {
+            if (c > 0 && lab[q - LB_TW - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW - 1));
+            if (lab[q - LB_TW] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW));
+            if (c + 1 < LB_TW && lab[q - LB_TW + 1] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW + 1));
+        }
+    }
+    __syncthreads();
+    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
+        const int r = q / LB_TW, c = q - r * LB_TW, i = i0 + r, j = j0 + c;
+        if (i >= H || j >= W) continue;
+        const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q);
+        const int rr = (int)root / LB_TW, rc = (int)root - rr * LB_TW;
+        parent[base + (size_t)i * W + j] = (uint32_t)(i0 + rr) * (uint32_t)W + (uint32_t)(j0 + rc);
+    }
+}
+
+// pixels on a tile border meet their W / NW / N / NE neighbours of equal label in the neighbouring tiles
+__global__ __launch_bounds__(MK_THREADS) void k_label_seams(const uint8_t *__restrict__ mask, int W, int H, uint32_t *__restrict__ parent)
+{
+    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
+    if (g >= (uint32_t)W * (uint32_t)H) return;
+    const int i = (int)(g / (uint32_t)W), j = (int)(g - (uint32_t)i * (uint32_t)W);
+    const bool top = (i % LB_TH) == 0, left = (j % LB_TW) == 0, right = (j % LB_TW) == LB_TW - 1;
+    if (!(top || left || right)) return;
+    const uint8_t *m = mask + (size_t)blockIdx.y * W * H;
+    uint32_t *par = parent + (size_t)blockIdx.y * W * H;
+    const uint8_t l = m[g];
+    if (!l) return;
+    if (left && j > 0 && m[g - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - 1);
+    if (i > 0) {
+        if ((top || left) && j > 0 && m[g - W - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W - 1);
+        if (top && m[g - W] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W);
+        if ((top || right) && j + 1 < W && m[g - W + 1] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W + 1);
+    }
+}
+
+// parent[g] = root; a root's statistics start at zero.  Writes race only with reads that accept any ancestor.
+__global__ __launch_bounds__(MK_THREADS) void k_label_flatten(const uint8_t *__restrict__ mask, int W, int H, uint32_t *__restrict__ parent,
+                                                              unsigned long long *__restrict__ stats)
+{
+    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
+    if (g >= (uint32_t)W * (uint32_t)H) return;
+    const size_t base = (size_t)blockIdx.y * W * H;
+    if (!mask[base + g]) return;
+    uint32_t *par = parent + base;
+    const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, g);
+    if (root != g) {
+        par[g] = root;
+    } else {
+        unsigned long long *st = stats + (base + g) * ST_WORDS;
+        for (int e = 0; e < ST_WORDS; ++e) st[e] = 0ull;
+    }
+}
+
+__device__ inline unsigned long long wave_sum(unsigned long long v)
+{
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// statistics at the root's index.  The lanes of a wave hold 64 consecutive pixels: those of equal root are summed in the wave and
+// their first lane sends one set of atomics.  depth may be null (disconnected_prune: the area alone).
+__global__ __launch_bounds__(MK_THREADS) void k_comp_stats(const uint8_t *__restrict__ mask, const uint16_t *__restrict__ depth, int W, int H,
+                                                           const uint32_t *__restrict__ parent, unsigned long long *__restrict__ stats)
+{
+    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
+    const size_t base = (size_t)blockIdx.y * W * H;
+    const int lane = (int)(threadIdx.x & 63);
+    bool active = false;
+    uint32_t root = NO_KEY;
+    unsigned long long d = 0, jd = 0, id = 0;
+    if (g < (uint32_t)W * (uint32_t)H && mask[base + g]) {
+        active = true;
+        root = parent[base + g];
+        d = depth ? depth[base + g] : 0;
+        const uint32_t i = g / (uint32_t)W, j = g - i * (uint32_t)W;
+        jd = (unsigned long long)j * d;
+        id = (unsigned long long)i * d;
+    }
+    unsigned long long todo = __ballot(active);
+    while (todo) {                                          // wave-uniform: one turn per distinct root among the 64 pixels
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t r0 = __shfl(root, leader);
+        const bool mine = active && root == r0;
+        const unsigned long long members = __ballot(mine);
+        const unsigned long long area = (unsigned long long)__popcll(members);
+        const unsigned long long n = (unsigned long long)__popcll(__ballot(mine && d > 0));
+        const unsigned long long sd = wave_sum(mine ? d : 0ull), sjd = wave_sum(mine ? jd : 0ull), sid = wave_sum(mine ? id : 0ull);
+        if (lane == leader) {
+            unsigned long long *st = stats + (base + r0) * ST_WORDS;
+            if (n) {
+                atomicAdd(&st[0], n);
+                atomicAdd(&st[1], sd);
+                atomicAdd(&st[2], sjd);
+                atomicAdd(&st[3], sid);
+            }
+            atomicAdd(reinterpret_cast<uint32_t *>(&st[4]), (uint32_t)area);
+        }
+        todo &= ~members;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ selection
+
+struct SelSlots {
+    uint32_t *ncomp;                 // [n][256] components of the label
+    uint32_t *key;                   // [n][256] duplicate: the kept root (NO_KEY none); disconnected: kept root + 1 (0 none)
+    unsigned long long *best;        // [n][256] duplicate: smallest distance's bit pattern; disconnected: largest area
+};
+
+__global__ __launch_bounds__(MK_THREADS) void k_select_init(SelSlots S, uint32_t total, int mode)
+{
+    const uint32_t q = blockIdx.x * MK_THREADS + threadIdx.x;
+    if (q >= total) return;
+    S.ncomp[q] = 0;
+    S.key[q] = mode == 0 ? NO_KEY : 0u;
+    S.best[q] = mode == 0 ? ~0ull : 0ull;
+}
+
+// distance of the component's mean world point from the scene centre; false without a valid-depth pixel or at 10000 and beyond
+__device__ inline bool comp_distance(const unsigned long long *st, const float *T, const MaskCam &c, const MaskCentre &ctr, double *out)
+{
+    if (st[0] == 0) return false;
+    const double n = (double)st[0], sd = (double)st[1], sjd = (double)st[2], sid = (double)st[3];
+    const double den = 1000.0 * n;
+    const double z = sd / den, x = (sjd - c.cx * sd) / (den * c.fx), y = (sid - c.cy * sd) / (den * c.fy);
+    const double dx = ((((double)T[0] * x + (double)T[1] * y) + (double)T[2] * z) + (double)T[3]) - ctr.c[0];
+    const double dy = ((((double)T[4] * x + (double)T[5] * y) + (double)T[6] * z) + (double)T[7]) - ctr.c[1];
+    const double dz = ((((double)T[8] * x + (double)T[9] * y) + (double)T[10] * z) + (double)T[11]) - ctr.c[2];
+    const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+    *out = dist;
+    return dist < 10000.0;
+}
+
+// PASS 0: count the label's components and reduce the best value; PASS 1: among the roots that hold it, the tie rule
+template <int PASS>
+__global__ __launch_bounds__(MK_THREADS) void k_select(const uint8_t *__restrict__ mask, int W, int H, const uint32_t *__restrict__ parent,
+                                                       const unsigned long long *__restrict__ stats, const float *__restrict__ poses, MaskCam c,
+                                                       MaskCentre ctr, uint32_t min_area, int mode, uint32_t frame0, SelSlots S)
+{
+    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
+    if (g >= (uint32_t)W * (uint32_t)H) return;
+    const size_t base = (size_t)blockIdx.y * W * H;
+    const uint8_t l = mask[base + g];
+    if (!l || parent[base + g] != g) return;
+    const uint32_t slot = (frame0 + blockIdx.y) * 256u + l;
+    const unsigned long long *st = stats + (base + g) * ST_WORDS;
+    const uint32_t area = (uint32_t)st[4];
+    if (PASS == 0) atomicAdd(&S.ncomp[slot], 1u);
+    if (area < min_area) return;
+    unsigned long long v;
+    if (mode == 0) {
+        double dist;
+        if (!comp_distance(st, poses + (size_t)(frame0 + blockIdx.y) * 16, c, ctr, &dist)) return;
+        v = (unsigned long long)__double_as_longlong(dist);      // non-negative doubles order as their bit patterns
+    } else {
+        v = area;
+    }
+    if (PASS == 0) {
+        if (mode == 0) atomicMin(&S.best[slot], v);
+        else atomicMax(&S.best[slot], v);
+    } else if (v == S.best[slot]) {
+        if (mode == 0) atomicMin(&S.key[slot], g);               // duplicate_prune compares with <: the first component wins
+        else atomicMax(&S.key[slot], g + 1u);                    // disconnected_prune compares with >=: the last one wins
+    }
+}
+
+__global__ __launch_bounds__(MK_THREADS) void k_prune_write(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ oob, int W, int H,
+                                                            const uint32_t *__restrict__ parent, int mode, uint32_t frame0, SelSlots S,
+                                                            uint8_t *__restrict__ out)
+{
+    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
+    if (g >= (uint32_t)W * (uint32_t)H) return;
+    const size_t base = (size_t)blockIdx.y * W * H;
+    const uint8_t l = mask[base + g];
+    uint8_t v = 0;
+    if (l) {
+        const uint32_t slot = (frame0 + blockIdx.y) * 256u + l, root = parent[base + g];
+        const bool keep = S.ncomp[slot] <= 1u || (mode == 0 ? S.key[slot] == root : S.key[slot] == root + 1u);
+        if (keep) v = l;
+    }
+    if (oob && oob[base + g] == 255) v = 255;
+    out[base + g] = v;
+}
+
+__global__ __launch_bounds__(MK_THREADS) void k_mask_lut(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ oob, size_t total, const uint8_t *__restrict__ lut,
+                                                         uint8_t *__restrict__ out, uint8_t *__restrict__ alpha)
+{
+    __shared__ uint8_t tab[256];
+    tab[threadIdx.x] = lut[threadIdx.x] ? 1 : 0;
+    __syncthreads();
+    const size_t q = ((size_t)blockIdx.x * MK_THREADS + threadIdx.x) * 4;
+    if (q >= total) return;
+    if (q + 4 <= total) {
+        const uint32_t m = *reinterpret_cast<const uint32_t *>(mask + q), ob = oob ? *reinterpret_cast<const uint32_t *>(oob + q) : 0u;
+        uint32_t r = 0;
+        for (int e = 0; e < 4; ++e) r |= (uint32_t)(tab[(m >> (8 * e)) & 0xffu] | (((ob >> (8 * e)) & 0xffu) ? 1u : 0u)) << (8 * e);
+        *reinterpret_cast<uint32_t *>(out + q) = r;
+        if (alpha) *reinterpret_cast<uint32_t *>(alpha + q) = (0x01010101u - r) * 255u;
+    } else {
+        for (size_t e = q; e < total; ++e) {
+            const uint8_t r = tab[mask[e]] | ((oob && oob[e]) ? 1 : 0);
+            out[e] = r;
+            if (alpha) alpha[e] = (uint8_t)(255 * (1 - r));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+
+int masks_check_frames(d2r_ctx *ctx, uint32_t n, uint32_t w, uint32_t h)
+{
+    if (n == 0 || w == 0 || h == 0) return d2r_fail(ctx, D2R_ERR_INVALID, "masks: n, width and height must be at least 1");
+    if ((uint64_t)w * h >= (1ull << 31)) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "masks: a frame must have fewer than 2^31 pixels");
+    if (n > 65535) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "masks: at most 65535 frames per call");
+    if ((uint64_t)n * w * h >= (1ull << 40)) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "masks: the batch must have fewer than 2^40 pixels");
+    return D2R_OK;
+}
+
+int masks_check_cam(d2r_ctx *ctx, const float *poses, uint32_t n, const double *K)
+{
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(K[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "masks: intrinsics must be finite");
+    if (K[0] == 0.0 || K[4] == 0.0) return d2r_fail(ctx, D2R_ERR_INVALID, "masks: focal lengths must not be 0");
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!std::isfinite(poses[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "masks: poses must be finite");
+    return D2R_OK;
+}
+
+int masks_events(d2r_ctx *ctx)
+{
+    for (auto &e : ctx->mask_ev)
+        if (!e) D2R_HIP(ctx, hipEventCreate(&e));
+    return D2R_OK;
+}
+
+// label, flatten and accumulate nf frames whose images start at mask / depth; parent and stats are the pass's workspace
+void masks_label(d2r_ctx *ctx, const uint8_t *mask, const uint16_t *depth, uint32_t nf, uint32_t w, uint32_t h, uint32_t *parent,
+                 unsigned long long *stats)
+{
+    const uint32_t px = w * h, gpx = (px + MK_THREADS - 1) / MK_THREADS;
+    hipLaunchKernelGGL(k_label_tiles, dim3((w + LB_TW - 1) / LB_TW, (h + LB_TH - 1) / LB_TH, nf), dim3(MK_THREADS), 0, ctx->stream, mask, (int)w,
+                       (int)h, parent);
+    hipLaunchKernelGGL(k_label_seams, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, mask, (int)w, (int)h, parent);
+    hipLaunchKernelGGL(k_label_flatten, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, mask, (int)w, (int)h, parent, stats);
+    hipLaunchKernelGGL(k_comp_stats, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, mask, depth, (int)w, (int)h, (const uint32_t *)parent, stats);
+}
+
+// frames per pass of d2r_masks_prune.  D2R_MASKS_WS_BYTES lowers (or raises) the workspace budget, so that a test can drive a small
+// batch through several passes, the way 100 frames of 1280 x 720 go with the default (26 frames per pass).
+uint32_t masks_pass_frames(uint32_t n, size_t px)
+{
+    size_t budget = MK_WS_BUDGET;
+    if (const char *v = getenv("D2R_MASKS_WS_BYTES")) {
+        char *end = nullptr;
+        const unsigned long long b = strtoull(v, &end, 10);
+        if (end != v && *end == 0 && b > 0) budget = (size_t)b;
+    }
+    const size_t per = px * (4 + 8 * ST_WORDS);
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, budget / per));
+}
+
+}  // namespace
+
+extern "C" {
+
+int d2r_scene_bound_masks(d2r_ctx *ctx, const uint16_t *depth_u16, uint32_t n, uint32_t w, uint32_t h, const float *poses, const double *K,
+                          const double *bounds, uint32_t window, uint8_t *out_u8, uint8_t *raw_out_u8)
+{
+    if (!ctx) return d2r_fail(ctx, D2R_ERR_INVALID, "null context");
+    if (!depth_u16 || !poses || !K || !bounds || !out_u8) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
+    if (window < 1 || window > 64) return d2r_fail(ctx, D2R_ERR_INVALID, "scene-bound masks: window must be 1 .. 64");
+    int rc;
+    if ((rc = masks_check_frames(ctx, n, w, h)) || (rc = masks_check_cam(ctx, poses, n, K))) return rc;
+    for (int i = 0; i < 6; ++i)
+        if (std::isnan(bounds[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "scene-bound masks: bounds must not be NaN");
+    D2R_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = masks_events(ctx))) return rc;
+    const size_t px = (size_t)w * h, ww = (w + 63) / 64, words = (size_t)n * h * ww;
+    const size_t o_pose = (px * 2 * n + 255) & ~(size_t)255, o_bits = (o_pose + (size_t)n * 64 + 255) & ~(size_t)255;
+    if ((rc = d2r_reserve(ctx, ctx->mask_in, o_bits + 2 * words * 8)) || (rc = d2r_reserve(ctx, ctx->mask_out, px * n))) return rc;
+    uint8_t *base = (uint8_t *)ctx->mask_in.p;
+    const uint16_t *d_depth = (const uint16_t *)base;
+    const float *d_pose = (const float *)(base + o_pose);
+    unsigned long long *b0 = (unsigned long long *)(base + o_bits), *b1 = b0 + words;
+    MaskCam c{K[0], K[4], K[2], K[5]};
+    MaskBox b{{bounds[0], bounds[1], -100.0}, {bounds[3], bounds[4], bounds[5]}};       // the reference overwrites zmin (data_loader.py:84)
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[0], ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(base, depth_u16, px * 2 * n, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(base + o_pose, poses, (size_t)n * 64, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[1], ctx->stream));
+    const uint32_t wpf = (uint32_t)(h * ww), W8 = (w + 7) / 8;
+    const dim3 g_unpack((uint32_t)(((size_t)h * W8 + MK_THREADS - 1) / MK_THREADS), n);
+    hipLaunchKernelGGL(k_scene_bounds, dim3((wpf + 3) / 4, n), dim3(MK_THREADS), 0, ctx->stream, d_depth, d_pose, c, b, (int)w, (int)h, (int)ww, b0);
+    if (raw_out_u8) {
+        hipLaunchKernelGGL(k_unpack, g_unpack, dim3(MK_THREADS), 0, ctx->stream, (const unsigned long long *)b0, (int)w, (int)h, (int)ww,
+                           (uint8_t *)ctx->mask_out.p);
+        D2R_HIP(ctx, hipMemcpyAsync(raw_out_u8, ctx->mask_out.p, px * n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    const dim3 g_morph((uint32_t)((ww + CL_TW - 1) / CL_TW), (h + CL_TR - 1) / CL_TR, n);
+    hipLaunchKernelGGL(k_morph<false>, g_morph, dim3(MK_THREADS), 0, ctx->stream, (const unsigned long long *)b0, b1, (int)w, (int)h, (int)ww, (int)window);
+    hipLaunchKernelGGL(k_morph<true>, g_morph, dim3(MK_THREADS), 0, ctx->stream, (const unsigned long long *)b1, b0, (int)w, (int)h, (int)ww, (int)window);
+    hipLaunchKernelGGL(k_unpack, g_unpack, dim3(MK_THREADS), 0, ctx->stream, (const unsigned long long *)b0, (int)w, (int)h, (int)ww,
+                       (uint8_t *)ctx->mask_out.p);
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[2], ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(out_u8, ctx->mask_out.p, px * n, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[3], ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->mask_timed = true;
+    return D2R_OK;
+}
+
+int d2r_masks_prune(d2r_ctx *ctx, int mode, const uint8_t *masks_u8, const uint16_t *depth_u16, const uint8_t *oob_u8, uint32_t n, uint32_t w,
+                    uint32_t h, const float *poses, const double *K, const double *centre, uint32_t min_area, uint8_t *out_u8)
+{
+    if (!ctx) return d2r_fail(ctx, D2R_ERR_INVALID, "null context");
+    if (mode != 0 && mode != 1) return d2r_fail(ctx, D2R_ERR_INVALID, "masks prune: mode must be 0 (duplicate) or 1 (disconnected)");
+    if (!masks_u8 || !out_u8 || (mode == 0 && (!depth_u16 || !poses || !K || !centre))) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = masks_check_frames(ctx, n, w, h))) return rc;
+    MaskCam c{1.0, 1.0, 0.0, 0.0};
+    MaskCentre ctr{{0.0, 0.0, 0.0}};
+    if (mode == 0) {
+        if ((rc = masks_check_cam(ctx, poses, n, K))) return rc;
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(centre[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "masks prune: scene centre must be finite");
+        c = MaskCam{K[0], K[4], K[2], K[5]};
+        ctr = MaskCentre{{centre[0], centre[1], centre[2]}};
+    }
+    D2R_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = masks_events(ctx))) return rc;
+    const size_t px = (size_t)w * h, tot = px * n;
+    const bool have_depth = mode == 0;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_depth = up(tot), o_oob = o_depth + up(have_depth ? tot * 2 : 0), o_pose = o_oob + up(oob_u8 ? tot : 0),
+                 o_n = o_pose + up((size_t)n * 64), o_key = o_n + up((size_t)n * 1024), o_best = o_key + up((size_t)n * 1024),
+                 in_total = o_best + up((size_t)n * 2048);
+    const uint32_t per = masks_pass_frames(n, px);
+    if ((rc = d2r_reserve(ctx, ctx->mask_in, in_total)) || (rc = d2r_reserve(ctx, ctx->mask_out, tot)) ||
+        (rc = d2r_reserve(ctx, ctx->mask_ws, (size_t)per * px * (4 + 8 * ST_WORDS))))
+        return rc;
+    uint8_t *base = (uint8_t *)ctx->mask_in.p;
+    const uint8_t *d_mask = base, *d_oob = oob_u8 ? base + o_oob : nullptr;
+    const uint16_t *d_depth = have_depth ? (const uint16_t *)(base + o_depth) : nullptr;
+    const float *d_pose = (const float *)(base + o_pose);
+    SelSlots S{(uint32_t *)(base + o_n), (uint32_t *)(base + o_key), (unsigned long long *)(base + o_best)};
+    unsigned long long *stats = (unsigned long long *)ctx->mask_ws.p;
+    uint32_t *parent = (uint32_t *)((uint8_t *)ctx->mask_ws.p + (size_t)per * px * 8 * ST_WORDS);
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[0], ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(base, masks_u8, tot, hipMemcpyHostToDevice, ctx->stream));
+    if (have_depth) {
+        D2R_HIP(ctx, hipMemcpyAsync(base + o_depth, depth_u16, tot * 2, hipMemcpyHostToDevice, ctx->stream));
+        D2R_HIP(ctx, hipMemcpyAsync(base + o_pose, poses, (size_t)n * 64, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (oob_u8) D2R_HIP(ctx, hipMemcpyAsync(base + o_oob, oob_u8, tot, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[1], ctx->stream));
+    hipLaunchKernelGGL(k_select_init, dim3((n * 256u + MK_THREADS - 1) / MK_THREADS), dim3(MK_THREADS), 0, ctx->stream, S, n * 256u, mode);
+    const uint32_t gpx = (uint32_t)((px + MK_THREADS - 1) / MK_THREADS);
+    for (uint32_t f0 = 0; f0 < n; f0 += per) {              // passes share the workspace; nothing waits in between
+        const uint32_t nf = std::min(per, n - f0);
+        const uint8_t *m = d_mask + (size_t)f0 * px;
+        masks_label(ctx, m, d_depth ? d_depth + (size_t)f0 * px : nullptr, nf, w, h, parent, stats);
+        hipLaunchKernelGGL(k_select<0>, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, m, (int)w, (int)h, (const uint32_t *)parent,
+                           (const unsigned long long *)stats, d_pose, c, ctr, min_area, mode, f0, S);
+        hipLaunchKernelGGL(k_select<1>, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, m, (int)w, (int)h, (const uint32_t *)parent,
+                           (const unsigned long long *)stats, d_pose, c, ctr, min_area, mode, f0, S);
+        hipLaunchKernelGGL(k_prune_write, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, m, d_oob ? d_oob + (size_t)f0 * px : nullptr, (int)w, (int)h,
+                           (const uint32_t *)parent, mode, f0, S, (uint8_t *)ctx->mask_out.p + (size_t)f0 * px);
+    }
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[2], ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(out_u8, ctx->mask_out.p, tot, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[3], ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->mask_timed = true;
+    return D2R_OK;
+}
+
+int d2r_masks_components(d2r_ctx *ctx, const uint8_t *mask_u8, const uint16_t *depth_u16, uint32_t w, uint32_t h, uint32_t *keys_out,
+                         uint32_t *area_out, uint64_t *sums_out)
+{
+    if (!ctx) return d2r_fail(ctx, D2R_ERR_INVALID, "null context");
+    if (!mask_u8 || !depth_u16 || !keys_out || !area_out || !sums_out) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = masks_check_frames(ctx, 1, w, h))) return rc;
+    D2R_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)w * h;
+    const size_t o_depth = (px + 255) & ~(size_t)255;
+    if ((rc = d2r_reserve(ctx, ctx->mask_in, o_depth + px * 2)) || (rc = d2r_reserve(ctx, ctx->mask_ws, px * (4 + 8 * ST_WORDS)))) return rc;
+    uint8_t *base = (uint8_t *)ctx->mask_in.p;
+    unsigned long long *stats = (unsigned long long *)ctx->mask_ws.p;
+    uint32_t *parent = (uint32_t *)((uint8_t *)ctx->mask_ws.p + px * 8 * ST_WORDS);
+    D2R_HIP(ctx, hipMemcpyAsync(base, mask_u8, px, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(base + o_depth, depth_u16, px * 2, hipMemcpyHostToDevice, ctx->stream));
+    masks_label(ctx, base, (const uint16_t *)(base + o_depth), 1, w, h, parent, stats);
+    D2R_HIP(ctx, hipGetLastError());
+    std::vector<unsigned long long> st(px * ST_WORDS);
+    D2R_HIP(ctx, hipMemcpyAsync(keys_out, parent, px * 4, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(st.data(), stats, px * 8 * ST_WORDS, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t g = 0; g < px; ++g) {                       // only roots carry statistics; label 0 has no component
+        const bool root = mask_u8[g] != 0 && keys_out[g] == (uint32_t)g;
+        if (!mask_u8[g]) keys_out[g] = NO_KEY;
+        area_out[g] = root ? (uint32_t)st[g * ST_WORDS + 4] : 0u;
+        for (int e = 0; e < 4; ++e) sums_out[g * 4 + e] = root ? (uint64_t)st[g * ST_WORDS + e] : 0ull;
+    }
+    return D2R_OK;
+}
+
+int d2r_masks_lut(d2r_ctx *ctx, const uint8_t *masks_u8, const uint8_t *oob_u8, uint32_t n, uint32_t w, uint32_t h, const uint8_t *lut,
+                  uint8_t *out_u8, uint8_t *alpha_out_u8)
+{
+    if (!ctx) return d2r_fail(ctx, D2R_ERR_INVALID, "null context");
+    if (!masks_u8 || !lut || !out_u8) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = masks_check_frames(ctx, n, w, h))) return rc;
+    D2R_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t tot = (size_t)w * h * n, seg = (tot + 255) & ~(size_t)255;
+    if ((rc = d2r_reserve(ctx, ctx->mask_in, 2 * seg + 256)) || (rc = d2r_reserve(ctx, ctx->mask_out, 2 * seg))) return rc;
+    uint8_t *base = (uint8_t *)ctx->mask_in.p, *ob = (uint8_t *)ctx->mask_out.p;
+    D2R_HIP(ctx, hipMemcpyAsync(base, masks_u8, tot, hipMemcpyHostToDevice, ctx->stream));
+    if (oob_u8) D2R_HIP(ctx, hipMemcpyAsync(base + seg, oob_u8, tot, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(base + 2 * seg, lut, 256, hipMemcpyHostToDevice, ctx->stream));
+    const size_t quads = (tot + 3) / 4;
+    hipLaunchKernelGGL(k_mask_lut, dim3((uint32_t)((quads + MK_THREADS - 1) / MK_THREADS)), dim3(MK_THREADS), 0, ctx->stream, (const uint8_t *)base,
+                       oob_u8 ? (const uint8_t *)(base + seg) : nullptr, tot, (const uint8_t *)(base + 2 * seg), ob, alpha_out_u8 ? ob + seg : nullptr);
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipMemcpyAsync(out_u8, ob, tot, hipMemcpyDeviceToHost, ctx->stream));
+    if (alpha_out_u8) D2R_HIP(ctx, hipMemcpyAsync(alpha_out_u8, ob + seg, tot, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return D2R_OK;
+}
+
+int d2r_masks_get_timing(d2r_ctx *ctx, double *ms_out)
+{
+    if (!ctx || !ms_out) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
+    if (!ctx->mask_timed) return d2r_fail(ctx, D2R_ERR_INVALID, "masks timing: no batch call has run on this context");
+    float up = 0.f, dev = 0.f, down = 0.f;
+    D2R_HIP(ctx, hipEventElapsedTime(&up, ctx->mask_ev[0], ctx->mask_ev[1]));
+    D2R_HIP(ctx, hipEventElapsedTime(&dev, ctx->mask_ev[1], ctx->mask_ev[2]));
+    D2R_HIP(ctx, hipEventElapsedTime(&down, ctx->mask_ev[2], ctx->mask_ev[3]));
+    ms_out[0] = up;
+    ms_out[1] = dev;
+    ms_out[2] = down;
+    return D2R_OK;
+}
+
+}  // extern "C"

@@ -375,14 +375,19 @@ int d2r_png_write_file_delta(const D2rPngBase &B, const uint8_t *rgb, const std:
     return D2R_OK;
 }
 
-// One RGB frame -> PNG bytes: colour type 2, bit depth 8, no interlace (any decoder returns the same pixels: PNG is lossless).
-int d2r_png_encode(const uint8_t *rgb, uint32_t w, uint32_t h, int level, std::vector<uint8_t> &out, std::string &err)
+// One frame of ch = 1 (grey), 3 (RGB) or 4 (RGBA) 8-bit channels -> PNG bytes: colour type 0 / 2 / 6, bit depth 8, no interlace
+// (any decoder returns the same pixels: PNG is lossless).
+int d2r_png_encode_channels(const uint8_t *rgb, uint32_t w, uint32_t h, uint32_t ch, int level, std::vector<uint8_t> &out, std::string &err)
 {
     if (!rgb || w == 0 || h == 0 || w > 32768 || h > 32768) {
         err = "bad image size";
         return D2R_ERR_INVALID;
     }
-    const size_t row = (size_t)w * 3;
+    if (ch != 1 && ch != 3 && ch != 4) {
+        err = "PNG channels must be 1, 3 or 4";
+        return D2R_ERR_INVALID;
+    }
+    const size_t row = (size_t)w * ch;
     // scratch buffers live as long as the worker thread: three fresh allocations of a third of a megabyte per frame are
     // mmap / munmap + page faults in glibc, and with many threads those serialise on the process' address-space lock —
     // measured on the 256-core MI355X host: 3.3 k files/s with 16 threads, 2.3 k with 64, 1.7 k with 128
@@ -400,8 +405,8 @@ int d2r_png_encode(const uint8_t *rgb, uint32_t w, uint32_t h, int level, std::v
         const uint8_t *src = rgb + row * y;
         if (fast) {
             dst[0] = 1;
-            dst[1] = src[0]; dst[2] = src[1]; dst[3] = src[2];
-            for (size_t i = 3; i < row; i++) dst[1 + i] = (uint8_t)(src[i] - src[i - 3]);
+            for (size_t i = 0; i < ch; i++) dst[1 + i] = src[i];
+            for (size_t i = ch; i < row; i++) dst[1 + i] = (uint8_t)(src[i] - src[i - ch]);
         } else {
             dst[0] = 0;
             memcpy(dst + 1, src, row);
@@ -450,7 +455,7 @@ int d2r_png_encode(const uint8_t *rgb, uint32_t w, uint32_t h, int level, std::v
     std::vector<uint8_t> ihdr;
     put32(ihdr, w);
     put32(ihdr, h);
-    const uint8_t tail[5] = {8, 2, 0, 0, 0};
+    const uint8_t tail[5] = {8, (uint8_t)(ch == 1 ? 0 : ch == 3 ? 2 : 6), 0, 0, 0};
     ihdr.insert(ihdr.end(), tail, tail + 5);
     chunk(out, "IHDR", ihdr.data(), ihdr.size());
     chunk(out, "IDAT", z.data(), cap);
@@ -458,11 +463,13 @@ int d2r_png_encode(const uint8_t *rgb, uint32_t w, uint32_t h, int level, std::v
     return D2R_OK;
 }
 
-int d2r_png_write_file(const uint8_t *rgb, uint32_t w, uint32_t h, int level, const std::string &path, std::string &err)
+int d2r_png_encode(const uint8_t *rgb, uint32_t w, uint32_t h, int level, std::vector<uint8_t> &out, std::string &err)
 {
-    thread_local std::vector<uint8_t> bytes;
-    int rc = d2r_png_encode(rgb, w, h, level, bytes, err);
-    if (rc) return rc;
+    return d2r_png_encode_channels(rgb, w, h, 3, level, out, err);
+}
+
+static int write_bytes(const std::vector<uint8_t> &bytes, const std::string &path, std::string &err)
+{
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) {
         err = "cannot open " + path + " for writing";
@@ -476,11 +483,23 @@ int d2r_png_write_file(const uint8_t *rgb, uint32_t w, uint32_t h, int level, co
     return D2R_OK;
 }
 
-// PNG bytes -> RGB.  Reads what PNG writers produce for 8-bit images without a palette: grey, grey + alpha, RGB,
-// RGBA (alpha dropped, grey replicated), all five scanline filters, IDAT split over any number of chunks.  Interlaced,
-// 16-bit and palette images are refused with a message (cv2.imwrite / PIL never write them for uint8 RGB arrays).
-int d2r_png_decode(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h, uint8_t *rgb_out, uint32_t *w_out,
-                   uint32_t *h_out, std::string &err)
+int d2r_png_write_file_channels(const uint8_t *px, uint32_t w, uint32_t h, uint32_t ch, int level, const std::string &path, std::string &err)
+{
+    thread_local std::vector<uint8_t> bytes;
+    int rc = d2r_png_encode_channels(px, w, h, ch, level, bytes, err);
+    return rc ? rc : write_bytes(bytes, path, err);
+}
+
+int d2r_png_write_file(const uint8_t *rgb, uint32_t w, uint32_t h, int level, const std::string &path, std::string &err)
+{
+    return d2r_png_write_file_channels(rgb, w, h, 3, level, path, err);
+}
+
+// The shared reader: header, inflate, scanline filters (all five), IDAT split over any number of chunks; grey, grey + alpha, RGB and
+// RGBA without a palette.  Interlaced and palette images are refused with a message.  pix (optional) receives the samples as stored, [h][w][ch] of
+// bits / 8 bytes each (16-bit samples big-endian); 16-bit files only with allow16.
+static int png_decode_samples(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h, bool allow16, std::vector<uint8_t> *pix, uint32_t *w_out,
+                              uint32_t *h_out, uint32_t *ch_out, uint32_t *bits_out, std::string &err)
 {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (!p || n < 8 + 25 || memcmp(p, sig, 8)) {
@@ -489,7 +508,7 @@ int d2r_png_decode(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h,
     }
     auto rd32 = [&](size_t at) { return ((uint32_t)p[at] << 24) | ((uint32_t)p[at + 1] << 16) | ((uint32_t)p[at + 2] << 8) | p[at + 3]; };
     size_t at = 8;
-    uint32_t w = 0, h = 0, ch = 0;
+    uint32_t w = 0, h = 0, ch = 0, bits = 8;
     std::vector<uint8_t> z;
     bool have_hdr = false, done = false;
     while (!done && at + 12 <= n) {
@@ -511,11 +530,12 @@ int d2r_png_decode(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h,
             w = rd32(at + 8);
             h = rd32(at + 12);
             const uint8_t depth = data[8], ctype = data[9], interlace = data[12];
-            if (depth != 8 || interlace != 0 || (ctype != 0 && ctype != 2 && ctype != 4 && ctype != 6)) {
+            if ((depth != 8 && !(allow16 && depth == 16)) || interlace != 0 || (ctype != 0 && ctype != 2 && ctype != 4 && ctype != 6)) {
                 err = "unsupported PNG (need 8-bit grey / RGB with or without alpha, not interlaced)";
                 return D2R_ERR_UNSUPPORTED;
             }
             ch = ctype == 0 ? 1 : ctype == 4 ? 2 : ctype == 2 ? 3 : 4;
+            bits = depth;
             have_hdr = true;
         } else if (!memcmp(type, "IDAT", 4)) {
             z.insert(z.end(), data, data + len);
@@ -530,12 +550,14 @@ int d2r_png_decode(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h,
     }
     if (w_out) *w_out = w;
     if (h_out) *h_out = h;
-    if (!rgb_out) return D2R_OK;
+    if (ch_out) *ch_out = ch;
+    if (bits_out) *bits_out = bits;
+    if (!pix) return D2R_OK;
     if ((want_w && want_w != w) || (want_h && want_h != h)) {
         err = "PNG is " + std::to_string(w) + "x" + std::to_string(h) + ", expected " + std::to_string(want_w) + "x" + std::to_string(want_h);
         return D2R_ERR_INVALID;
     }
-    const size_t row = (size_t)w * ch;
+    const size_t bpp = (size_t)ch * (bits / 8), row = (size_t)w * bpp;
     std::vector<uint8_t> raw((row + 1) * h);
     uLongf got = (uLongf)raw.size();
     if (uncompress(raw.data(), &got, z.data(), (uLong)z.size()) != Z_OK || got != raw.size()) {
@@ -543,11 +565,12 @@ int d2r_png_decode(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h,
         return D2R_ERR_INVALID;
     }
     std::vector<uint8_t> prev(row, 0), cur(row);
+    pix->resize(row * h);
     for (uint32_t y = 0; y < h; y++) {
         const uint8_t ft = raw[(row + 1) * y];
         const uint8_t *src = &raw[(row + 1) * y + 1];
         for (size_t i = 0; i < row; i++) {
-            const int a = i >= ch ? cur[i - ch] : 0, b = prev[i], c = i >= ch ? prev[i - ch] : 0;
+            const int a = i >= bpp ? cur[i - bpp] : 0, b = prev[i], c = i >= bpp ? prev[i - bpp] : 0;
             int pred;
             switch (ft) {
             case 0: pred = 0; break;
@@ -565,14 +588,77 @@ int d2r_png_decode(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h,
             }
             cur[i] = (uint8_t)(src[i] + pred);
         }
+        memcpy(pix->data() + (size_t)y * row, cur.data(), row);
+        prev.swap(cur);
+    }
+    return D2R_OK;
+}
+
+// PNG bytes -> RGB.  Reads what PNG writers produce for 8-bit images without a palette: grey, grey + alpha, RGB, RGBA (alpha dropped,
+// grey replicated).  16-bit images are refused here with a message (cv2.imwrite / PIL never write them for uint8 RGB arrays).
+int d2r_png_decode(const uint8_t *p, size_t n, uint32_t want_w, uint32_t want_h, uint8_t *rgb_out, uint32_t *w_out,
+                   uint32_t *h_out, std::string &err)
+{
+    std::vector<uint8_t> pix;
+    uint32_t w = 0, h = 0, ch = 0;
+    int rc = png_decode_samples(p, n, want_w, want_h, false, rgb_out ? &pix : nullptr, &w, &h, &ch, nullptr, err);
+    if (rc) return rc;
+    if (w_out) *w_out = w;
+    if (h_out) *h_out = h;
+    if (!rgb_out) return D2R_OK;
+    for (uint32_t y = 0; y < h; y++) {
+        const uint8_t *cur = pix.data() + (size_t)y * w * ch;
         uint8_t *dst = rgb_out + (size_t)y * w * 3;
         for (uint32_t x = 0; x < w; x++) {
             const uint8_t *q = &cur[(size_t)x * ch];
             if (ch <= 2) dst[3 * x] = dst[3 * x + 1] = dst[3 * x + 2] = q[0];
             else { dst[3 * x] = q[0]; dst[3 * x + 1] = q[1]; dst[3 * x + 2] = q[2]; }
         }
-        prev.swap(cur);
     }
+    return D2R_OK;
+}
+
+static int read_bytes(const std::string &path, std::vector<uint8_t> &bytes, std::string &err)
+{
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) {
+        err = "cannot open " + path;
+        return D2R_ERR_INVALID;
+    }
+    uint8_t buf[1 << 16];
+    size_t k;
+    while ((k = fread(buf, 1, sizeof buf, f)) > 0) bytes.insert(bytes.end(), buf, buf + k);
+    fclose(f);
+    return D2R_OK;
+}
+
+// A grey PNG of 8 or 16 bits -> its samples: uint8 [h][w] or uint16 [h][w] in host byte order (`bits` says which the caller
+// expects; depth files are 16-bit, mask files 8-bit).  out may be null to read the header alone.
+int d2r_png_read_file_grey(const std::string &path, uint32_t bits, uint32_t want_w, uint32_t want_h, void *out, uint32_t *w_out, uint32_t *h_out,
+                           uint32_t *bits_out, uint32_t *ch_out, std::string &err)
+{
+    std::vector<uint8_t> bytes, pix;
+    int rc = read_bytes(path, bytes, err);
+    if (rc) return rc;
+    uint32_t w = 0, h = 0, ch = 0, fb = 0;
+    rc = png_decode_samples(bytes.data(), bytes.size(), want_w, want_h, true, out ? &pix : nullptr, &w, &h, &ch, &fb, err);
+    if (rc) {
+        err = path + ": " + err;
+        return rc;
+    }
+    if (w_out) *w_out = w;
+    if (h_out) *h_out = h;
+    if (bits_out) *bits_out = fb;
+    if (ch_out) *ch_out = ch;
+    if (!out) return D2R_OK;
+    if (ch != 1 || fb != bits) {
+        err = path + ": expected a " + std::to_string(bits) + "-bit grey PNG, found " + std::to_string(fb) + " bits x " + std::to_string(ch) + " channels";
+        return D2R_ERR_INVALID;
+    }
+    const size_t px = (size_t)w * h;
+    if (bits == 8) memcpy(out, pix.data(), px);
+    else
+        for (size_t i = 0; i < px; i++) ((uint16_t *)out)[i] = (uint16_t)(((uint16_t)pix[2 * i] << 8) | pix[2 * i + 1]);
     return D2R_OK;
 }
 
@@ -790,6 +876,39 @@ int d2r_png_read_batch(const char *dir, const uint32_t *indices, uint32_t first_
     pool.wait(-1);
     std::string err;
     int rc = pool.take_error(err);
+    return rc ? d2r_fail(nullptr, rc, err) : D2R_OK;
+}
+
+int d2r_png_write_channels(const uint8_t *pixels, uint32_t w, uint32_t h, uint32_t channels, const char *path, int level)
+{
+    if (!pixels || !path) return d2r_fail(nullptr, D2R_ERR_INVALID, "null argument");
+    std::string err;
+    int rc = d2r_png_write_file_channels(pixels, w, h, channels, level, path, err);
+    return rc ? d2r_fail(nullptr, rc, err) : D2R_OK;
+}
+
+int d2r_png_read_rgb(const char *path, uint32_t w, uint32_t h, uint8_t *rgb_out)
+{
+    if (!path || !rgb_out) return d2r_fail(nullptr, D2R_ERR_INVALID, "null argument");
+    std::string err;
+    int rc = d2r_png_read_file(path, w, h, rgb_out, nullptr, nullptr, err);
+    return rc ? d2r_fail(nullptr, rc, err) : D2R_OK;
+}
+
+int d2r_png_info(const char *path, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bits)
+{
+    if (!path || !w || !h || !channels || !bits) return d2r_fail(nullptr, D2R_ERR_INVALID, "null argument");
+    std::string err;
+    int rc = d2r_png_read_file_grey(path, 0, 0, 0, nullptr, w, h, bits, channels, err);
+    return rc ? d2r_fail(nullptr, rc, err) : D2R_OK;
+}
+
+int d2r_png_read_grey(const char *path, uint32_t bits, uint32_t w, uint32_t h, void *out)
+{
+    if (!path || !out) return d2r_fail(nullptr, D2R_ERR_INVALID, "null argument");
+    if (bits != 8 && bits != 16) return d2r_fail(nullptr, D2R_ERR_INVALID, "grey PNG: bits must be 8 or 16");
+    std::string err;
+    int rc = d2r_png_read_file_grey(path, bits, w, h, out, nullptr, nullptr, nullptr, nullptr, err);
     return rc ? d2r_fail(nullptr, rc, err) : D2R_OK;
 }
 

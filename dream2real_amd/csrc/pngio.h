@@ -9,6 +9,11 @@
 #include <vector>
 
 int d2r_png_encode(const uint8_t *rgb, uint32_t w, uint32_t h, int level, std::vector<uint8_t> &out, std::string &err);
+// ch = 1 grey, 3 RGB, 4 RGBA
+int d2r_png_encode_channels(const uint8_t *px, uint32_t w, uint32_t h, uint32_t ch, int level, std::vector<uint8_t> &out, std::string &err);
+int d2r_png_write_file_channels(const uint8_t *px, uint32_t w, uint32_t h, uint32_t ch, int level, const std::string &path, std::string &err);
+int d2r_png_read_file_grey(const std::string &path, uint32_t bits, uint32_t want_w, uint32_t want_h, void *out, uint32_t *w_out, uint32_t *h_out,
+                           uint32_t *bits_out, uint32_t *ch_out, std::string &err);
 int d2r_png_write_file(const uint8_t *rgb, uint32_t w, uint32_t h, int level, const std::string &path, std::string &err);
 int d2r_png_decode(const uint8_t *bytes, size_t n, uint32_t want_w, uint32_t want_h, uint8_t *rgb_out, uint32_t *w_out,
                    uint32_t *h_out, std::string &err);

@@ -1,0 +1,65 @@
+"""The geometric half of the reference's segmentation stage (segmentation/XMem_infer.py:213-236, 264-351) on the GPU: connected
+components of a raw label image, the area rule, the component nearest the scene centre (duplicate_prune) or the largest
+(disconnected_prune), the out-of-scene overwrite, and the XMem_masks/rgb_%04d.png files everything downstream reads.  The rule
+is DESIGN.md section 2d.
+
+Running SAM or XMem is out of scope: whatever produced the raw label images (XMem in the reference), `refine_masks` is the
+body of the `segment_associate` loop from there on and `load_cached_masks` its cache branch."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from . import _lib
+
+MIN_COMPONENT_AREA = 200          # XMem_infer.py:289, :340
+
+
+def _np(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def depth_to_u16(depth):
+    """The reference's (depth * 1000).astype(np.uint16) on its fp16-metre depth, the product in float16; uint16 input is
+    taken as millimetres already."""
+    d = _np(depth)
+    if d.dtype == np.uint16:
+        return np.ascontiguousarray(d)
+    with np.errstate(over="ignore"):
+        return (d.astype(np.float16) * np.float16(1000)).astype(np.uint16)
+
+
+def duplicate_prune(mask, depth, T_WC, intrinsics, scene_centre, *, ctx):
+    """reference XMem_infer.py:264-316: per label keep the component (area >= 200 when there are several) whose mean 3-D point is
+    nearest the scene centre.  mask uint8 [H,W], depth fp16 metres [H,W] -> uint8 [H,W]."""
+    m = _np(mask).astype(np.uint8)
+    return _lib.masks_prune(ctx, 0, m[None], depth_to_u16(depth)[None], None, _np(T_WC).reshape(1, 16), _np(intrinsics), _np(scene_centre),
+                            MIN_COMPONENT_AREA)[0]
+
+
+def disconnected_prune(mask, *, ctx):
+    """reference XMem_infer.py:318-351: per label keep the largest component (area >= 200 when there are several)."""
+    return _lib.masks_prune(ctx, 1, _np(mask).astype(np.uint8)[None], min_area=MIN_COMPONENT_AREA)[0]
+
+
+def refine_masks(raw_masks, depths, T_WC, intrinsics, out_scene_bound_masks, scene_centre, out_dir, *, ctx):
+    """The batched body of segment_associate's loop (:213-236) for the associated frames: duplicate_prune of every raw label image,
+    255 where the scene-bound mask is 255, written to <out_dir>/XMem_masks/rgb_%04d.png.  One GPU call for all frames.
+    -> uint8 [N,H,W]."""
+    m = _np(raw_masks).astype(np.uint8)
+    oob = None if out_scene_bound_masks is None else _np(out_scene_bound_masks).astype(np.uint8)
+    refined = _lib.masks_prune(ctx, 0, m, depth_to_u16(depths), oob, _np(T_WC).reshape(-1, 16), _np(intrinsics), _np(scene_centre),
+                               MIN_COMPONENT_AREA)
+    if out_dir is not None:
+        mask_dir = os.path.join(out_dir, "XMem_masks")
+        os.makedirs(mask_dir, exist_ok=True)
+        for k in range(refined.shape[0]):
+            _lib.png_write_channels(refined[k], os.path.join(mask_dir, "rgb_%04d.png" % k))
+    return refined
+
+
+def load_cached_masks(out_dir, n):
+    """segment_associate's cache branch: <out_dir>/XMem_masks/rgb_%04d.png for n frames -> uint8 [n,H,W]."""
+    mask_dir = os.path.join(out_dir, "XMem_masks")
+    return np.stack([_lib.png_read_grey(os.path.join(mask_dir, "rgb_%04d.png" % k), 8) for k in range(n)])

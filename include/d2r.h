@@ -694,6 +694,49 @@ D2R_API int d2r_tsdf_extract(d2r_tsdf *vol, float weight_threshold, const float 
 D2R_API int d2r_obj_write(const char *path, const float *vertices, uint32_t n_vertices, const uint32_t *triangles,
                           uint32_t n_triangles, const uint8_t *keep);
 
+/* 8-bit images of 1 (grey), 3 (RGB) or 4 (RGBA) interleaved channels -> a PNG file (mask files, the RGBA task images); a grey PNG
+ * of 8 or 16 bits -> uint8 / uint16 [h][w] in host byte order (mask files, the 16-bit millimetre depth files; w, h: the expected
+ * size, 0 = any); d2r_png_info reads the header.  Host only. */
+D2R_API int d2r_png_write_channels(const uint8_t *pixels, uint32_t w, uint32_t h, uint32_t channels, const char *path, int level);
+D2R_API int d2r_png_info(const char *path, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bits);
+D2R_API int d2r_png_read_rgb(const char *path, uint32_t w, uint32_t h, uint8_t *rgb_out);   /* one 8-bit file of any name -> [h][w][3] */
+D2R_API int d2r_png_read_grey(const char *path, uint32_t bits, uint32_t w, uint32_t h, void *out);
+
+/* ------------------------------------------------- scene-bound masks and the pruning of segmentation masks
+ *
+ * replaces reference data_loader.py:71-122 (remove_background: Open3D back-projection, six planes and a height cut, a
+ * closing by a 50 x 50 rectangle, per frame on the CPU) and segmentation/XMem_infer.py:264-351 (duplicate_prune,
+ * disconnected_prune: cv2.connectedComponents per label per frame) with the out-of-scene overwrite of :224.  The rule is
+ * DESIGN.md section 2d.  Both batch calls upload all n frames once, run without a host synchronisation between frames and
+ * return when the result is in the caller's memory.  Frames are [n][h][w], w * h < 2^31; poses host [n][16] fp32 row-major
+ * camera-to-world; K host [9] row-major fp64.
+ */
+
+/* bounds host [6]: xmin ymin zmin xmax ymax zmax (zmin is replaced by -100 as the reference does); window 1 .. 64 (the
+ * reference: 50); out_u8 host [n][h][w] 0 / 255 after the closing; raw_out_u8 (optional) the same before it. */
+D2R_API int d2r_scene_bound_masks(d2r_ctx *ctx, const uint16_t *depth_u16, uint32_t n, uint32_t w, uint32_t h, const float *poses,
+                                  const double *K, const double *bounds, uint32_t window, uint8_t *out_u8, uint8_t *raw_out_u8);
+
+/* mode 0 duplicate_prune (depth_u16, poses, K, centre host [3] required), 1 disconnected_prune (they may be NULL).  masks_u8
+ * label images, 0 = background; oob_u8 (optional): where it is 255 the output is 255; min_area 200 in the reference. */
+D2R_API int d2r_masks_prune(d2r_ctx *ctx, int mode, const uint8_t *masks_u8, const uint16_t *depth_u16, const uint8_t *oob_u8,
+                            uint32_t n, uint32_t w, uint32_t h, const float *poses, const double *K, const double *centre,
+                            uint32_t min_area, uint8_t *out_u8);
+
+/* Parity hook, one frame: keys_out host [h][w] the order key (raster index of the first pixel) of each pixel's component,
+ * 0xffffffff where the label is 0; area_out host [h][w] and sums_out host [h][w][4] (n, sum d, sum j d, sum i d over the
+ * pixels with d16 > 0) hold a component's statistics at its order key and 0 elsewhere. */
+D2R_API int d2r_masks_components(d2r_ctx *ctx, const uint8_t *mask_u8, const uint16_t *depth_u16, uint32_t w, uint32_t h,
+                                 uint32_t *keys_out, uint32_t *area_out, uint64_t *sums_out);
+
+/* out = (lut[mask] != 0) | (oob != 0) as 0 / 1 (oob_u8 optional), alpha_out_u8 (optional) = 255 (1 - out).  lut host [256]. */
+D2R_API int d2r_masks_lut(d2r_ctx *ctx, const uint8_t *masks_u8, const uint8_t *oob_u8, uint32_t n, uint32_t w, uint32_t h,
+                          const uint8_t *lut, uint8_t *out_u8, uint8_t *alpha_out_u8);
+
+/* Device-event times of the last d2r_scene_bound_masks / d2r_masks_prune on this context: ms_out host [3] = upload, kernels,
+ * download, in milliseconds. */
+D2R_API int d2r_masks_get_timing(d2r_ctx *ctx, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif
