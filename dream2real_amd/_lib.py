@@ -23,6 +23,8 @@ EXPORTS = [
     "d2r_png_read_batch", "d2r_png_size", "d2r_savetxt", "d2r_ingp_validate", "d2r_debug_gemm_fp8", "d2r_ctx_get_option", "d2r_png_write_batch_bg",
     "d2r_pcd_create", "d2r_pcd_destroy", "d2r_pcd_render", "d2r_pcd_render_score_host",
     "d2r_tsdf_create", "d2r_tsdf_destroy", "d2r_tsdf_integrate", "d2r_tsdf_read_voxels", "d2r_tsdf_extract", "d2r_obj_write",
+    "d2r_tsdf_grid", "d2r_tsdf_touch_bits", "d2r_tsdf_solid_points",
+    "d2r_sdfphys_create", "d2r_sdfphys_destroy", "d2r_sdfphys_check", "d2r_sdfphys_get_timing",
     "d2r_png_write_channels", "d2r_png_info", "d2r_png_read_grey", "d2r_png_read_rgb",
     "d2r_scene_bound_masks", "d2r_masks_prune", "d2r_masks_components", "d2r_masks_lut", "d2r_masks_get_timing",
 ]
@@ -132,6 +134,7 @@ def load() -> C.CDLL:
     lib.d2r_phys_destroy.restype = None
     lib.d2r_pcd_destroy.restype = None
     lib.d2r_tsdf_destroy.restype = None
+    lib.d2r_sdfphys_destroy.restype = None
     for name in EXPORTS:
         getattr(lib, name)          # every declared symbol must be exported
     if lib.d2r_abi_version() != ABI_VERSION:

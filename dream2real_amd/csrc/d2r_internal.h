@@ -223,6 +223,10 @@ struct PerDeviceOnce {
 int d2r_fail(d2r_ctx *ctx, int code, const std::string &msg);
 int d2r_reserve(d2r_ctx *ctx, d2r_ctx::Buf &b, size_t bytes);
 
+// phys.hip: the host side the two physics pre-filters (hulls + GJK in phys.hip, points against the TSDF field in sdfphys.hip) share
+int d2r_phys_orientations(d2r_ctx *, const d2r_phys_params *, uint32_t N, uint64_t *oris_out);      // checks N against sample_res -> orientations per position
+std::vector<uint8_t> d2r_phys_orientation_mask(const d2r_phys_params *, const float *pose_batch, const uint8_t *valid_io, uint32_t oris);   // [oris] 0: duplicate orientation / not regraspable
+
 // api.hip: what the entry points that score frames share
 struct d2r_clip;
 uint32_t d2r_pass_size(const d2r_ctx *, const d2r_clip *clip, size_t px);      // candidates per pass: option "chunk" under the model's (clip, optional) and the ray queue's (px per frame, 0 = no rays) 32-bit bounds

@@ -314,6 +314,53 @@ __global__ __launch_bounds__(256) void k_phys_check(PhysKernelParams P, const fl
     if (lane == 0) valid[pose] = ok ? 1 : 0;
 }
 
+// the pose grid of a check: N must be the product of sample_res; -> orientations per position
+int d2r_phys_orientations(d2r_ctx *ctx, const d2r_phys_params *prm, uint32_t N, uint64_t *oris_out)
+{
+    uint64_t expect = 1, oris = 1;
+    for (int i = 0; i < 6; i++) {
+        if (prm->sample_res[i] == 0) return d2r_fail(ctx, D2R_ERR_INVALID, "sample_res entries must be positive");
+        expect *= prm->sample_res[i];
+        if (i >= 3) oris *= prm->sample_res[i];
+    }
+    if (expect != N) return d2r_fail(ctx, D2R_ERR_INVALID, "pose count does not match sample_res");
+    *oris_out = oris;
+    return D2R_OK;
+}
+
+// orientation uniqueness (reference :260-278: greedy over the orientations of the FIRST position, then tiled)
+// and the regrasp rule (:281-301) are a few thousand 3x3 compares at most: host side, uploaded as one mask
+std::vector<uint8_t> d2r_phys_orientation_mask(const d2r_phys_params *prm, const float *pose_batch, const uint8_t *valid_io, uint32_t oris)
+{
+    std::vector<uint8_t> mask(oris, 1);
+    std::vector<uint32_t> kept;
+    for (uint32_t i = 0; i < oris; i++) {
+        const float *a = pose_batch + (size_t)i * 16;
+        bool seen = false;
+        for (uint32_t k : kept) {
+            const float *b = pose_batch + (size_t)k * 16;
+            bool close = true;
+            for (int r = 0; r < 3 && close; r++)
+                for (int c = 0; c < 3; c++)
+                    if (!(fabsf(a[r * 4 + c] - b[r * 4 + c]) <= 0.01f + 1e-5f * fabsf(b[r * 4 + c]))) {   // torch.isclose(atol=0.01)
+                        close = false;
+                        break;
+                    }
+            if (close) { seen = true; break; }
+        }
+        if (seen) mask[i] = 0;
+        else kept.push_back(i);
+    }
+    if (prm->disallow_regrasp)
+        for (uint32_t i = 0; i < oris; i++) {
+            if (!mask[i] || !valid_io[i]) { mask[i] = 0; continue; }     // reference :285-287 reads valid_so_far of the first position
+            const float *a = pose_batch + (size_t)i * 16;
+            const float zy = a[6], zz = a[10];                           // the object's z axis: column 2 of the rotation
+            if (!(zz > 0.9f || -zy > 0.9f)) mask[i] = 0;
+        }
+    return mask;
+}
+
 extern "C" {
 
 int d2r_phys_create(d2r_ctx *ctx, const float *movable_verts, const uint32_t *movable_offsets, uint32_t n_movable,
@@ -407,14 +454,8 @@ int d2r_phys_check(d2r_ctx *ctx, const d2r_phys *phys, const d2r_phys_params *pr
                    uint8_t *valid_io)
 {
     if (!ctx || !phys || !prm || !pose_batch || !valid_io) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
-    uint64_t expect = 1, oris = 1;
-    for (int i = 0; i < 6; i++) {
-        if (prm->sample_res[i] == 0) return d2r_fail(ctx, D2R_ERR_INVALID, "sample_res entries must be positive");
-        expect *= prm->sample_res[i];
-        if (i >= 3) oris *= prm->sample_res[i];
-    }
-    if (expect != N) return d2r_fail(ctx, D2R_ERR_INVALID, "pose count does not match sample_res");
-    if (N == 0) return D2R_OK;
+    uint64_t oris = 1;
+    if (int rc = d2r_phys_orientations(ctx, prm, N, &oris)) return rc;
     PhysKernelParams P;
     if (!invert4(prm->init_pose, P.inv_init)) return d2r_fail(ctx, D2R_ERR_INVALID, "init_pose is singular");
     P.table_z = prm->table_z;
@@ -425,37 +466,7 @@ int d2r_phys_check(d2r_ctx *ctx, const d2r_phys *phys, const d2r_phys_params *pr
     P.oris_per_pos = (uint32_t)oris;
     if (!(prm->margin >= 0.f) || !(prm->margin < 1.f)) return d2r_fail(ctx, D2R_ERR_INVALID, "collision margin must be in [0, 1) metres");
     P.margin2 = 2.f * prm->margin;
-    // orientation uniqueness (reference :260-278: greedy over the orientations of the FIRST position, then tiled)
-    // and the regrasp rule (:281-301) are a few thousand 3x3 compares at most: host side, uploaded as one mask
-    std::vector<uint8_t> mask(oris, 1);
-    {
-        std::vector<uint32_t> kept;
-        for (uint32_t i = 0; i < oris; i++) {
-            const float *a = pose_batch + (size_t)i * 16;
-            bool seen = false;
-            for (uint32_t k : kept) {
-                const float *b = pose_batch + (size_t)k * 16;
-                bool close = true;
-                for (int r = 0; r < 3 && close; r++)
-                    for (int c = 0; c < 3; c++)
-                        if (!(fabsf(a[r * 4 + c] - b[r * 4 + c]) <= 0.01f + 1e-5f * fabsf(b[r * 4 + c]))) {   // torch.isclose(atol=0.01)
-                            close = false;
-                            break;
-                        }
-                if (close) { seen = true; break; }
-            }
-            if (seen) mask[i] = 0;
-            else kept.push_back(i);
-        }
-        if (prm->disallow_regrasp)
-            for (uint32_t i = 0; i < oris; i++) {
-                if (!mask[i] || !valid_io[i]) { mask[i] = 0; continue; }     // reference :285-287 reads valid_so_far of the first position
-                const float *a = pose_batch + (size_t)i * 16;
-                const float zx = a[2], zy = a[6], zz = a[10];                // the object's z axis: column 2 of the rotation
-                (void)zx;
-                if (!(zz > 0.9f || -zy > 0.9f)) mask[i] = 0;
-            }
-    }
+    const std::vector<uint8_t> mask = d2r_phys_orientation_mask(prm, pose_batch, valid_io, (uint32_t)oris);
     (void)hipSetDevice(ctx->device);
     int rc;
     if ((rc = d2r_reserve(ctx, ctx->poses, (size_t)N * 64))) return rc;

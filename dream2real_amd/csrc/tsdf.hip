@@ -11,6 +11,8 @@
 //   k_mark_blocks  one lane per valid pixel walks its ray over [z - trunc, z + trunc] in voxel steps and stamps the blocks
 //   k_integrate    one workgroup per block stamped this frame, lanes along x: the running average, frame by frame
 //   k_mc_*         classify cubes, mark crossed edges, scan counts in (z, y, x) order, emit vertices, emit triangles
+//   k_tsdf_touch_bits / k_tsdf_solid_*   the volume as the point-against-field physics backend reads it (DESIGN.md section 2e,
+//                  sdfphys.hip): one "touch" bit per voxel, and the centres of the observed solid voxels in (z, y, x) order
 // Every value is written by ordinary vector stores from C++.
 #include <math.h>
 #include <string.h>
@@ -51,7 +53,7 @@ struct d2r_tsdf {
     uint32_t *stamp = nullptr;      // [n_blocks] 1 + index of the last frame that touched the block
     uint8_t *ever = nullptr;        // [n_blocks]
     uint32_t *list = nullptr;       // [n_blocks] blocks of the current frame (order does not matter: voxels are independent)
-    uint32_t *counters = nullptr;   // [0] length of list, [1] valid pixels of the frame, [2..3] vertex / triangle totals
+    uint32_t *counters = nullptr;   // [0] length of list, [1] valid pixels of the frame, [2..3] vertex / triangle totals, [4] solid voxels
     uint32_t frame = 0;
     d2r_ctx::Buf depth_in, mask_in, zbuf;
     // the last extraction, kept for the fill call
@@ -408,6 +410,117 @@ __global__ __launch_bounds__(TSDF_THREADS) void k_mc_emit(const float2 *__restri
     }
 }
 
+// ------------------------------------------------------------------------------------------------ field and points (section 2e)
+
+// touch[g] = w >= thr && tsdf * trunc <= contact, packed along x: bit x & 31 of word x >> 5, rows of wpr = ceil(nx / 32) words.
+// One wave per 64 voxels of a row: its ballot is two words (the second only where the row still has one).
+__global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_touch_bits(const float2 *__restrict__ vox, TsdfGrid G, uint32_t wpr, uint32_t segs,
+                                                                  uint64_t n_waves, float thr, float contact, uint32_t *__restrict__ words)
+{
+    const uint64_t wave = (uint64_t)blockIdx.x * (TSDF_THREADS / 64) + (threadIdx.x >> 6);
+    if (wave >= n_waves) return;                                    // whole waves leave: the ballot below sees all 64 lanes
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t row = wave / segs;                               // z * ny + y
+    const uint32_t seg = (uint32_t)(wave - row * segs), x = seg * 64u + lane;
+    bool t = false;
+    if (x < G.nv[0]) {
+        const float2 s = vox[row * G.nv[0] + x];
+        t = s.y >= thr && s.x * G.trunc <= contact;
+    }
+    const unsigned long long b = __ballot(t);
+    if (lane == 0) words[row * wpr + 2u * seg] = (uint32_t)b;
+    if (lane == 32 && 2u * seg + 1u < wpr) words[row * wpr + 2u * seg + 1u] = (uint32_t)(b >> 32);
+}
+
+// solid voxels (w >= thr && tsdf <= 0) of a 4096-voxel chunk: thread t looks at voxels s * 256 + t, s = 0 .. 15 (a wave reads
+// 64 neighbours per step); bit s of the result
+__device__ __forceinline__ uint32_t solid_mask16(const float2 *__restrict__ vox, uint64_t first, float thr)
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 16; ++s) {
+        const float2 v = vox[first + s * TSDF_THREADS + threadIdx.x];
+        m |= (v.y >= thr && v.x <= 0.f ? 1u : 0u) << s;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_solid_count(const float2 *__restrict__ vox, float thr, uint32_t *__restrict__ chunk)
+{
+    __shared__ uint32_t part[TSDF_THREADS];
+    part[threadIdx.x] = (uint32_t)__popc(solid_mask16(vox, (uint64_t)blockIdx.x * MC_CHUNK, thr));
+    __syncthreads();
+    for (uint32_t s = TSDF_THREADS / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) chunk[blockIdx.x] = part[0];
+}
+
+// exclusive scan of the chunk counts in place (one workgroup, the shape of k_mc_scan_chunks); the total to counters[4]
+__global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_solid_scan(uint32_t *__restrict__ chunk, uint32_t nchunks, uint32_t *__restrict__ counters)
+{
+    __shared__ uint32_t part[TSDF_THREADS];
+    const uint32_t per = (nchunks + TSDF_THREADS - 1) / TSDF_THREADS, lo = min(nchunks, threadIdx.x * per), hi = min(nchunks, lo + per);
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += chunk[i];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t i = 0; i < TSDF_THREADS; i++) {
+            const uint32_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        counters[4] = run;
+    }
+    __syncthreads();
+    uint32_t run = part[threadIdx.x];
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t v = chunk[i];
+        chunk[i] = run;
+        run += v;
+    }
+}
+
+// the centres (float)g * voxel of the solid voxels, in voxel order: a chunk's 16 steps x 4 waves are 64 runs of 64 voxels
+__global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_solid_emit(const float2 *__restrict__ vox, const uint32_t *__restrict__ chunk, TsdfGrid G,
+                                                                  float thr, float *__restrict__ xyz, uint32_t n_points)
+{
+    __shared__ uint32_t runs[16 * (TSDF_THREADS / 64)];
+    const uint64_t first = (uint64_t)blockIdx.x * MC_CHUNK;
+    const uint32_t mine = solid_mask16(vox, first, thr);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t s = 0; s < 16; ++s) {
+        const unsigned long long b = __ballot((mine >> s) & 1u);
+        if (lane == 0) runs[s * (TSDF_THREADS / 64) + wave] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = chunk[blockIdx.x];
+        for (uint32_t i = 0; i < 16 * (TSDF_THREADS / 64); i++) {
+            const uint32_t v = runs[i];
+            runs[i] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t s = 0; s < 16; ++s) {
+        const unsigned long long b = __ballot((mine >> s) & 1u);
+        const uint32_t at = runs[s * (TSDF_THREADS / 64) + wave] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (((mine >> s) & 1u) && at < n_points) {
+            uint32_t px, py, pz;
+            mc_xyz(first + s * TSDF_THREADS + threadIdx.x, G, px, py, pz);
+            xyz[(size_t)at * 3 + 0] = (float)(G.b0[0] * D2R_TSDF_BLOCK + (int32_t)px) * G.voxel;
+            xyz[(size_t)at * 3 + 1] = (float)(G.b0[1] * D2R_TSDF_BLOCK + (int32_t)py) * G.voxel;
+            xyz[(size_t)at * 3 + 2] = (float)(G.b0[2] * D2R_TSDF_BLOCK + (int32_t)pz) * G.voxel;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 // rigid inverse [R^T | -R^T t] of a row-major 4x4, fp64, fixed order (as pcd.hip composes its matrices)
@@ -674,6 +787,83 @@ int d2r_tsdf_extract(d2r_tsdf *v, float weight_threshold, const float *crop, dou
     if (keep) memcpy(keep, m.keep.data(), m.keep.size());
     if (centre) memcpy(centre, m.centre, 24);
     return D2R_OK;
+}
+
+int d2r_tsdf_grid(const d2r_tsdf *v, int32_t *b0, uint32_t *nv, float *voxel, float *trunc)
+{
+    if (!v || !b0 || !nv || !voxel || !trunc) return d2r_fail(v ? v->ctx : nullptr, D2R_ERR_INVALID, "null argument");
+    for (int a = 0; a < 3; ++a) {
+        b0[a] = v->G.b0[a];
+        nv[a] = v->G.nv[a];
+    }
+    *voxel = v->G.voxel;
+    *trunc = v->G.trunc;
+    return D2R_OK;
+}
+
+int d2r_tsdf_touch_bits(d2r_tsdf *v, float weight_threshold, float contact, uint32_t *words_out)
+{
+    if (!v || !words_out) return tsdf_fail(v, D2R_ERR_INVALID, "null argument");
+    d2r_ctx *ctx = v->ctx;
+    if (!(weight_threshold > 0.f) || !std::isfinite(weight_threshold) || !std::isfinite(contact))
+        return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_touch_bits: weight_threshold must be > 0 and contact finite");
+    D2R_HIP(ctx, hipSetDevice(v->device));
+    const TsdfGrid &G = v->G;
+    const uint32_t wpr = (G.nv[0] + 31u) / 32u, segs = (G.nv[0] + 63u) / 64u;
+    const uint64_t rows = (uint64_t)G.nv[1] * G.nv[2], n_waves = rows * segs;
+    const size_t bytes = (size_t)rows * wpr * 4;
+    uint32_t *d_words = nullptr;
+    int rc = tsdf_alloc(ctx, d_words, bytes, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_tsdf_touch_bits, dim3((uint32_t)((n_waves + 3) / 4)), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, G, wpr, segs, n_waves,
+                       weight_threshold, contact, d_words);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(words_out, d_words, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d_words);
+    if (e != hipSuccess) return d2r_fail(ctx, D2R_ERR_DEVICE, std::string("d2r_tsdf_touch_bits: ") + hipGetErrorString(e));
+    return D2R_OK;
+}
+
+int d2r_tsdf_solid_points(d2r_tsdf *v, float weight_threshold, uint32_t *n_points, float *xyz)
+{
+    if (!v || !n_points) return tsdf_fail(v, D2R_ERR_INVALID, "null argument");
+    d2r_ctx *ctx = v->ctx;
+    if (!(weight_threshold > 0.f) || !std::isfinite(weight_threshold))
+        return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_solid_points: weight_threshold must be > 0");
+    D2R_HIP(ctx, hipSetDevice(v->device));
+    const uint32_t nchunks = (uint32_t)(v->n_vox / MC_CHUNK), cap = *n_points;
+    uint32_t *chunk = nullptr;
+    float *d_xyz = nullptr;
+    auto body = [&]() -> int {
+        int r;
+        if ((r = tsdf_alloc(ctx, chunk, (size_t)nchunks * 4, false))) return r;
+        hipLaunchKernelGGL(k_tsdf_solid_count, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, weight_threshold, chunk);
+        hipLaunchKernelGGL(k_tsdf_solid_scan, dim3(1), dim3(TSDF_THREADS), 0, ctx->stream, chunk, nchunks, v->counters);
+        D2R_HIP(ctx, hipGetLastError());
+        uint32_t tot = 0;
+        D2R_HIP(ctx, hipMemcpyAsync(&tot, v->counters + 4, 4, hipMemcpyDeviceToHost, ctx->stream));
+        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *n_points = tot;
+        if (tot == 0)
+            return d2r_fail(ctx, D2R_ERR_INVALID,
+                            "TSDF volume holds no solid voxel: the object was seen in no frame (no voxel reached the weight threshold with "
+                            "tsdf <= 0)");
+        if (!xyz) return D2R_OK;
+        if (cap < tot) return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_solid_points: buffer smaller than the point set");
+        if ((r = tsdf_alloc(ctx, d_xyz, (size_t)tot * 12, false))) return r;
+        hipLaunchKernelGGL(k_tsdf_solid_emit, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, chunk, v->G, weight_threshold, d_xyz, tot);
+        D2R_HIP(ctx, hipGetLastError());
+        D2R_HIP(ctx, hipMemcpyAsync(xyz, d_xyz, (size_t)tot * 12, hipMemcpyDeviceToHost, ctx->stream));
+        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return D2R_OK;
+    };
+    const int rc = body();
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    for (void *p : {(void *)chunk, (void *)d_xyz})
+        if (p) (void)hipFree(p);
+    return rc;
 }
 
 }  // extern "C"

@@ -14,6 +14,10 @@ get_phys_models :25-229; its TSDF branch is `get_phys_models` below, Poisson and
 `g` group: VHACD writes one per convex part) into the convex hull of its vertices, so an object is a compound of
 convex parts: `hulls_from_obj` reads exactly that.  Objects may instead carry vertex arrays (`phys_hull` /
 `phys_hulls`), which take precedence — tests and callers without mesh files use them.
+
+A second backend needs no convex parts: `get_phys_models(..., phys_backend="tsdf")` writes
+`sdf_{id}.npz` — the TSDF volume's "touch" bits and its observed solid voxels — and when every object's `phys_model` is such
+a file, `create_unsupcol_check` answers the same three questions point against field (`SdfPhysicsShapes`).
 """
 from __future__ import annotations
 
@@ -161,8 +165,106 @@ class PhysicsShapes:
         return valid.astype(bool)
 
 
-def _np(x):
-    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+SDF_CONTACT = 2 * PYBULLET_MESH_MARGIN      # the distance at which the hull backend calls two parts "in contact"
+_SDF_GRID_KEYS = ("b0", "nv", "voxel", "trunc")
+
+
+def _phys_params(sample_res, init_pose, table_z, unsup_thresh, perturb, stability_check, disallow_regrasp, margin):
+    return _lib.PhysParams((C.c_uint32 * 6)(*[int(x) for x in sample_res]),
+                           (C.c_float * 16)(*np.asarray(init_pose, np.float64).reshape(16)),
+                           float(table_z), float(unsup_thresh), (C.c_float * 3)(*[float(x) for x in GRAVITY_DIRECTION]),
+                           float(perturb), int(bool(stability_check)), int(bool(disallow_regrasp)), float(margin))
+
+
+def save_sdf_model(path, grid, weight_threshold, contact, words, points):
+    """sdf_{id}.npz: the grid header (b0, nv, voxel, trunc), the two constants the field was cut with, the touch words
+    uint32 [nz, ny, ceil(nx / 32)] and the solid points float32 [n, 3]."""
+    b0, nv, voxel, trunc = grid
+    np.savez_compressed(path, b0=np.asarray(b0, np.int32), nv=np.asarray(nv, np.uint32), voxel=np.float32(voxel), trunc=np.float32(trunc),
+                        weight_threshold=np.float32(weight_threshold), contact=np.float32(contact),
+                        words=np.ascontiguousarray(words, np.uint32), points=np.ascontiguousarray(points, np.float32).reshape(-1, 3))
+
+
+def load_sdf_model(path) -> dict:
+    with np.load(path) as z:
+        m = {k: z[k] for k in z.files}
+    nx, ny, nz = (int(v) for v in m["nv"])
+    if m["words"].shape != (nz, ny, (nx + 31) // 32):
+        raise ValueError(f"{path}: touch words of shape {m['words'].shape} do not fit the grid {nx} x {ny} x {nz}")
+    return m
+
+
+class SdfPhysicsShapes:
+    """d2r_sdfphys: the static scene as one touch bit per voxel (`words`: one grid or a stack of grids, ORed) and the movable
+    object's solid points, on the GPU."""
+
+    def __init__(self, ctx, b0, nv, voxel, words, points):
+        self.ctx = ctx
+        b0 = np.ascontiguousarray(b0, np.int32).reshape(3)
+        nv = np.ascontiguousarray(nv, np.uint32).reshape(3)
+        nx, ny, nz = (int(v) for v in nv)
+        w = np.ascontiguousarray(words, np.uint32)
+        if w.ndim == 3:
+            w = w[None]
+        if w.ndim != 4 or w.shape[1:] != (nz, ny, (nx + 31) // 32):
+            raise ValueError(f"touch words of shape {w.shape} do not fit the grid {nx} x {ny} x {nz}")
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.d2r_sdfphys_create(ctx.h, _lib.ptr(b0), _lib.ptr(nv), C.c_float(voxel), _lib.ptr(w), C.c_uint32(w.shape[0]),
+                                             _lib.ptr(pts), C.c_uint32(pts.shape[0]), C.byref(h)))
+        self.h = h
+        self.n_points = pts.shape[0]
+
+    @classmethod
+    def from_files(cls, ctx, static_paths, movable_path):
+        """The static objects' sdf_{id}.npz files (their grids must be one grid) and the movable object's."""
+        mov = load_sdf_model(movable_path)
+        stat = [load_sdf_model(p) for p in static_paths]
+        if not stat:
+            raise ValueError("no static object to check against")
+        for p, m in zip(list(static_paths) + [movable_path], stat + [mov]):
+            for k in _SDF_GRID_KEYS:
+                if not np.array_equal(m[k], stat[0][k]):
+                    raise ValueError(f"{p}: grid differs from {static_paths[0]} in {k} ({m[k]} against {stat[0][k]}); the volumes of a "
+                                     "scene must be built over the same scene_bounds")
+        if len(mov["points"]) == 0:
+            raise ValueError(f"{movable_path}: the movable object has no solid points (seen in no frame)")
+        return cls(ctx, stat[0]["b0"], stat[0]["nv"], float(stat[0]["voxel"]), np.stack([m["words"] for m in stat]), mov["points"])
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.d2r_sdfphys_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def check(self, pose_batch, valid_so_far, sample_res, init_pose, table_z, unsup_thresh=0.02,
+              stability_check=True, disallow_regrasp=False, perturb=0.04, margin=0.0) -> np.ndarray:
+        """PhysicsShapes.check's arguments; `margin` is ignored (the contact distance is in the bits)."""
+        poses = np.ascontiguousarray(np.asarray(pose_batch, np.float64).reshape(-1, 16), np.float32)
+        valid = np.ascontiguousarray(np.asarray(valid_so_far).astype(np.uint8).reshape(-1))
+        assert valid.shape[0] == poses.shape[0]
+        prm = _phys_params(sample_res, init_pose, table_z, unsup_thresh, perturb, stability_check, disallow_regrasp, 0.0)
+        self.ctx.check(self.ctx.lib.d2r_sdfphys_check(self.ctx.h, self.h, C.byref(prm), _lib.ptr(poses),
+                                                      C.c_uint32(poses.shape[0]), _lib.ptr(valid)))
+        return valid.astype(bool)
+
+    def timing(self):
+        """(upload, kernel, download) of the last check, device-event milliseconds."""
+        ms = np.zeros(3, np.float64)
+        self.ctx.check(self.ctx.lib.d2r_sdfphys_get_timing(self.ctx.h, self.h, _lib.ptr(ms)))
+        return tuple(float(x) for x in ms)
+
+
+def _is_sdf_model(obj) -> bool:
+    if getattr(obj, "phys_hulls", None) is not None or getattr(obj, "phys_hull", None) is not None:
+        return False
+    model = getattr(obj, "phys_model", None)
+    return isinstance(model, (str, os.PathLike)) and os.fspath(model).endswith(".npz")
 
 
 def create_unsupcol_check(ctx, task_model, sample_res, embodied, unsup_thresh=0.02, lazy_phys_mods=True, stability_check=True,
@@ -173,7 +275,33 @@ def create_unsupcol_check(ctx, task_model, sample_res, embodied, unsup_thresh=0.
     movable object, otherwise every object of the scene model — all but the movable one static.  The handles are what
     stands for PyBullet's body ids here: per static object the list of its convex parts' vertex arrays, and for the
     movable object a one-element list holding its parts; `unsupcol_check.shapes` is the GPU-side object (close() frees it).
-    `movable_hull` / `static_hulls` override the lookup with explicit vertex arrays."""
+    `movable_hull` / `static_hulls` override the lookup with explicit vertex arrays.
+
+    When every object's `phys_model` is an sdf_{id}.npz (get_phys_models(phys_backend="tsdf")) the check runs point against
+    field (SdfPhysicsShapes; `margin` does not apply, the contact distance is in the bits) and the handles are the files'
+    paths; a mix of .npz and mesh files is a ValueError."""
+    if movable_hull is None and static_hulls is None:
+        objs = [task_model.task_bground_obj, task_model.movable_obj] if lazy_phys_mods else list(task_model.scene_model.objs)
+        sdf = [o for o in objs if _is_sdf_model(o)]
+        if sdf and len(sdf) != len(objs):
+            other = next(o for o in objs if not _is_sdf_model(o))
+            raise ValueError(f"create_unsupcol_check: the objects mix physics backends: {sdf[0].phys_model} is a TSDF field "
+                             f"(phys_backend='tsdf') and {getattr(other, 'phys_model', None)} is not; build all of them with one backend")
+        if sdf:
+            if not any(o is task_model.movable_obj for o in objs):
+                raise ValueError("the movable object is not among the objects to check")
+            static_paths = [os.fspath(o.phys_model) for o in objs if o is not task_model.movable_obj]
+            movable_path = os.fspath(task_model.movable_obj.phys_model)
+            field = SdfPhysicsShapes.from_files(ctx, static_paths, movable_path)
+
+            def sdf_unsupcol_check(pose_batch, task_model, valid_so_far, disallow_regrasp=embodied):
+                import torch
+                valid = field.check(_np(pose_batch), _np(valid_so_far), sample_res, _np(task_model.movable_obj.pose),
+                                    float(_np(task_model.scene_model.scene_centre)[2]), unsup_thresh, stability_check, disallow_regrasp)
+                return torch.from_numpy(valid)
+
+            sdf_unsupcol_check.shapes = field
+            return sdf_unsupcol_check, static_paths, [movable_path]      # the handles: the objects' field files
     if movable_hull is not None or static_hulls is not None:
         mov = [np.asarray(movable_hull, np.float64).reshape(-1, 3)] if movable_hull is not None else object_hulls(task_model.movable_obj)
         static_objs = [[np.asarray(h, np.float64).reshape(-1, 3)] for h in static_hulls] if static_hulls is not None else \
@@ -271,6 +399,33 @@ class TsdfVolume:
         return dict(vertices=v, triangles=t, clusters=lab, keep=keep.astype(bool), centre=centre)
 
 
+    def grid(self):
+        """-> (b0 int32 [3] first block per axis, nv uint32 [3] voxels per axis (x, y, z), voxel, trunc)."""
+        b0, nv = np.zeros(3, np.int32), np.zeros(3, np.uint32)
+        voxel, trunc = C.c_float(0), C.c_float(0)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_grid(self.h, _lib.ptr(b0), _lib.ptr(nv), C.byref(voxel), C.byref(trunc)))
+        return b0, nv, np.float32(voxel.value), np.float32(trunc.value)
+
+    def touch_bits(self, weight_threshold: float = TSDF_WEIGHT_THRESHOLD, contact: float = SDF_CONTACT) -> np.ndarray:
+        """-> uint32 [nz, ny, ceil(nx / 32)]: bit x & 31 of word x >> 5 = the voxel is observed and within `contact` of the
+        surface or behind it."""
+        nx, ny, nz = (int(v) for v in self.grid()[1])
+        words = np.zeros((nz, ny, (nx + 31) // 32), np.uint32)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_touch_bits(self.h, C.c_float(weight_threshold), C.c_float(contact), _lib.ptr(words)))
+        return words
+
+    def solid_points(self, weight_threshold: float = TSDF_WEIGHT_THRESHOLD) -> np.ndarray:
+        """-> float32 [n, 3]: the centres of the observed solid voxels (weight >= threshold, tsdf <= 0) in (z, y, x) order."""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_solid_points(self.h, C.c_float(weight_threshold), C.byref(n), None))
+        xyz = np.zeros((n.value, 3), np.float32)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_solid_points(self.h, C.c_float(weight_threshold), C.byref(n), _lib.ptr(xyz)))
+        return xyz
+
+
+PHYS_BACKENDS = ("hulls", "tsdf")
+
+
 def vhacd_convexify(concave_path: str, convex_path: str, obj_id: int):
     """The reference's VHACD call (:185-193) through PyBullet, when PyBullet is installed.  Nothing is downloaded."""
     try:
@@ -284,7 +439,8 @@ def vhacd_convexify(concave_path: str, convex_path: str, obj_id: int):
 
 
 def get_phys_models(depths, cam_poses, intrinsics, masks, num_objs, scene_bounds, embodied=False, save_dir=None, vis=False,
-                    use_cache=True, use_phys_tsdf=False, use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None):
+                    use_cache=True, use_phys_tsdf=False, use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None,
+                    phys_backend="hulls"):
     """reference vision_3d/physics_utils.py:25-229 -> (mesh_paths, init_poses): per object id the path of mesh_{id}.obj and
     its initial pose (float32 4x4 tensor: identity with the mesh centre as translation).
 
@@ -292,12 +448,19 @@ def get_phys_models(depths, cam_poses, intrinsics, masks, num_objs, scene_bounds
     frames on the GPU, write mesh_concave_{id}.obj and init_pose_{id}.txt, and hand the concave mesh
     to `convexify(concave_path, convex_path, obj_id)` (default: PyBullet's VHACD with the reference's arguments).  The
     Poisson branch (use_phys_tsdf=False) is not built.  `vis` (an Open3D window) and `embodied` (PyBullet's connection)
-    are accepted and ignored.  `ctx`: an engine.Context (default: a fresh one on device 0)."""
+    are accepted and ignored.  `ctx`: an engine.Context (default: a fresh one on device 0).
+
+    phys_backend="tsdf" (DESIGN.md section 2e): fuse and write mesh_concave_{id}.obj and init_pose_{id}.txt as above, skip
+    `convexify`, write sdf_{id}.npz (save_sdf_model) from the same volume and return those paths; with use_cache the
+    sdf_{id}.npz paths are returned."""
     import torch
+    if phys_backend not in PHYS_BACKENDS:
+        raise ValueError(f"get_phys_models: phys_backend must be one of {PHYS_BACKENDS}, got {phys_backend!r}")
+    model_name = "sdf_{}.npz" if phys_backend == "tsdf" else "mesh_{}.obj"
     if use_cache:
         mesh_paths, init_poses = [], []
         for obj_id in range(num_objs):
-            mesh_paths.append(os.path.join(save_dir, f"mesh_{obj_id}.obj"))
+            mesh_paths.append(os.path.join(save_dir, model_name.format(obj_id)))
             init_poses.append(torch.tensor(np.loadtxt(f"{save_dir}/init_pose_{obj_id}.txt")).float())
         return mesh_paths, init_poses
     if not use_phys_tsdf:
@@ -326,6 +489,9 @@ def get_phys_models(depths, cam_poses, intrinsics, masks, num_objs, scene_bounds
                     mesh = vol.extract(TSDF_WEIGHT_THRESHOLD, bounds, TSDF_CLUSTER_KEEP)
                 except _lib.D2RError as e:
                     raise ValueError(f"get_phys_models: object {obj_id} has no TSDF surface inside scene_bounds ({e})") from e
+                if phys_backend == "tsdf":
+                    field = (vol.grid(), TSDF_WEIGHT_THRESHOLD, SDF_CONTACT, vol.touch_bits(TSDF_WEIGHT_THRESHOLD, SDF_CONTACT),
+                             vol.solid_points(TSDF_WEIGHT_THRESHOLD))
             finally:
                 vol.close()
             init_pose = torch.eye(4)
@@ -334,9 +500,13 @@ def get_phys_models(depths, cam_poses, intrinsics, masks, num_objs, scene_bounds
             _lib.savetxt(os.path.join(save_dir, f"init_pose_{obj_id}.txt"), init_pose.numpy())
             concave = os.path.join(save_dir, f"mesh_concave_{obj_id}.obj")
             _lib.obj_write(concave, mesh["vertices"], mesh["triangles"], mesh["keep"])
-            convex = os.path.join(save_dir, f"mesh_{obj_id}.obj")
-            convexify(concave, convex, obj_id)
-            mesh_paths.append(convex)
+            if phys_backend == "tsdf":
+                model = os.path.join(save_dir, model_name.format(obj_id))
+                save_sdf_model(model, *field)
+            else:
+                model = os.path.join(save_dir, f"mesh_{obj_id}.obj")
+                convexify(concave, model, obj_id)
+            mesh_paths.append(model)
     finally:
         if own_ctx:
             ctx.close()
@@ -344,10 +514,11 @@ def get_phys_models(depths, cam_poses, intrinsics, masks, num_objs, scene_bounds
 
 
 def create_lazy_phys_mods(scene_model, movable_obj, scene_bounds, save_dir, embodied=False, vis=False, use_cache=False, use_phys_tsdf=True,
-                          use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None):
+                          use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None, phys_backend="hulls"):
     """reference scene_model.py:116-125 (TaskModel.create_lazy_phys_mods): two physics models, the movable object (mask 1)
     and everything else (mask 0) -> ([bground_phys, movable_phys], [bground_init_pose, movable_init_pose])."""
     fg_bg_masks = [(_np(m) == movable_obj.mask_idx).astype(np.uint8) for m in scene_model.masks]
     return get_phys_models(scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, fg_bg_masks, num_objs=2,
                            scene_bounds=scene_bounds, embodied=embodied, save_dir=save_dir, vis=vis, use_cache=use_cache,
-                           use_phys_tsdf=use_phys_tsdf, use_vis_pcds=use_vis_pcds, single_view_idx=single_view_idx, ctx=ctx, convexify=convexify)
+                           use_phys_tsdf=use_phys_tsdf, use_vis_pcds=use_vis_pcds, single_view_idx=single_view_idx, ctx=ctx, convexify=convexify,
+                           phys_backend=phys_backend)

@@ -694,6 +694,44 @@ D2R_API int d2r_tsdf_extract(d2r_tsdf *vol, float weight_threshold, const float 
 D2R_API int d2r_obj_write(const char *path, const float *vertices, uint32_t n_vertices, const uint32_t *triangles,
                           uint32_t n_triangles, const uint8_t *keep);
 
+/* ------------------------------------------------- the physics pre-filter straight from TSDF volumes
+ *
+ * A second backend of the pre-filter beside d2r_phys_*: no mesh and no convex parts.  All volumes of a scene are created
+ * over the same bounds and so share one grid.  The static scene is one "touch" bit per voxel, the movable object the centres
+ * of its observed solid voxels; a pose collides / is supported / is stable when any of its points lands on a set bit under
+ * the probe translations of d2r_phys_check (the pose; lowered by unsup_thresh along gravity; the lowered pose pushed by
+ * +-perturb along x, then y).
+ */
+
+/* The grid of a volume: b0 host [3] first block per axis (block b holds voxels 16 b .. 16 b + 15, voxel g sits at g * voxel),
+ * nv host [3] voxels per axis (x, y, z). */
+D2R_API int d2r_tsdf_grid(const d2r_tsdf *vol, int32_t *b0, uint32_t *nv, float *voxel, float *trunc);
+
+/* touch[g] = weight[g] >= weight_threshold && tsdf[g] * trunc <= contact (fp32), packed along x: bit x & 31 of word x >> 5,
+ * words_out host [nz][ny][ceil(nx / 32)].  The reference setting: weight_threshold 3, contact 0.002 (twice PyBullet's mesh
+ * margin).  Unobserved voxels never touch.  Synchronous. */
+D2R_API int d2r_tsdf_touch_bits(d2r_tsdf *vol, float weight_threshold, float contact, uint32_t *words_out);
+
+/* The centres (float)g * voxel of the voxels with weight >= weight_threshold && tsdf <= 0 (the observed solid shell), in
+ * (z, y, x) order.  *n_points: the capacity of xyz on entry, the count on return; xyz host [n][3], NULL = count only.  A
+ * volume without such a voxel is D2R_ERR_INVALID ("seen in no frame").  Synchronous. */
+D2R_API int d2r_tsdf_solid_points(d2r_tsdf *vol, float weight_threshold, uint32_t *n_points, float *xyz);
+
+typedef struct d2r_sdfphys d2r_sdfphys;
+/* words host [n_static_grids][nz][ny][ceil(nx / 32)]: the touch bits of the static objects, all on the grid (b0, nv, voxel);
+ * they are ORed.  points host [n_points][3]: the movable object's points, world frame at its initial pose.  Refused with
+ * D2R_ERR_INVALID: null pointers, no grid, no points, nv[a] = 0 or > 2^20, |b0[a]| > 2^19, more than 2^31 voxels. */
+D2R_API int d2r_sdfphys_create(d2r_ctx *ctx, const int32_t *b0, const uint32_t *nv, float voxel, const uint32_t *words,
+                               uint32_t n_static_grids, const float *points, uint32_t n_points, d2r_sdfphys **out);
+D2R_API void d2r_sdfphys_destroy(d2r_sdfphys *h);
+/* d2r_phys_check's arguments and verdict sequence.  params->margin is IGNORED: the contact distance was baked into the bits
+ * (d2r_tsdf_touch_bits' contact).  params->init_pose must be rigid; T = pose inv(init_pose) is composed in fp64 with the
+ * rigid inverse and rounded once.  A point whose voxel lies outside the grid, or is not finite, touches nothing. */
+D2R_API int d2r_sdfphys_check(d2r_ctx *ctx, d2r_sdfphys *h, const d2r_phys_params *params, const float *pose_batch, uint32_t N,
+                              uint8_t *valid_io);
+/* Device-event times of the handle's last check: ms_out host [3] = upload, kernel, download, in milliseconds. */
+D2R_API int d2r_sdfphys_get_timing(d2r_ctx *ctx, const d2r_sdfphys *h, double *ms_out);
+
 /* 8-bit images of 1 (grey), 3 (RGB) or 4 (RGBA) interleaved channels -> a PNG file (mask files, the RGBA task images); a grey PNG
  * of 8 or 16 bits -> uint8 / uint16 [h][w] in host byte order (mask files, the 16-bit millimetre depth files; w, h: the expected
  * size, 0 = any); d2r_png_info reads the header.  Host only. */
