@@ -440,8 +440,9 @@ int d2r_nerf_create(d2r_ctx *ctx, const d2r_nerf_desc *d, d2r_nerf **out)
     const uint32_t aabb = d->aabb_scale ? d->aabb_scale : 1u;
     if ((aabb & (aabb - 1u)) || aabb > 128u) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "aabb_scale must be a power of two <= 128");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    d2r_nerf *m = new d2r_nerf();
+    std::unique_ptr<d2r_nerf> m(new d2r_nerf());
     m->ctx = ctx;
+    m->device = ctx->device;
     NerfParams &P = m->P;
     P.n_levels = d->n_levels;
     LevelMeta lv[D2R_MAX_LEVELS];
@@ -456,21 +457,15 @@ int d2r_nerf_create(d2r_ctx *ctx, const d2r_nerf_desc *d, d2r_nerf **out)
         lm.offset = d->level_offset[l];
         uint64_t r3 = (uint64_t)lm.res * lm.res * lm.res;
         lm.hashed = r3 > lm.size;
-        if (lm.hashed && (lm.size & (lm.size - 1))) {
-            delete m;
+        if (lm.hashed && (lm.size & (lm.size - 1)))
             return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "hashed levels must have a power-of-two size");
-        }
         if (lm.hashed) {
-            if (hash_size && hash_size != lm.size) {
-                delete m;
+            if (hash_size && hash_size != lm.size)
                 return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "hashed levels must share one table size");
-            }
             hash_size = lm.size;
         }
-        if ((uint64_t)lm.offset + lm.size > d->n_entries) {
-            delete m;
+        if ((uint64_t)lm.offset + lm.size > d->n_entries)
             return d2r_fail(ctx, D2R_ERR_INVALID, "level table exceeds n_entries");
-        }
         if (!lm.hashed && prefix) n_dense++;
         if (lm.hashed) prefix = false;
         if (!lm.hashed && !prefix && (int)l >= n_dense) n_dense = -1000;   // dense after hashed: irregular
@@ -652,44 +647,34 @@ int d2r_nerf_create(d2r_ctx *ctx, const d2r_nerf_desc *d, d2r_nerf **out)
     }
 
     const size_t grid_bytes = tab.size() * 4;
-    if (grid_bytes >= (1ull << 32)) {
-        delete m;
-        return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "grid larger than 4 GiB");
-    }
-    bool ok = hipMalloc(&m->d_grid, grid_bytes) == hipSuccess &&
-              hipMalloc(&m->d_bricks, bricks.size() * 8) == hipSuccess &&
-              hipMalloc(&m->d_wfrag, wf.size() * 2) == hipSuccess &&
-              hipMalloc(&m->d_brick_tab, std::max<size_t>(brick_tab.size(), 1) * 4) == hipSuccess &&
-              hipMalloc(&m->d_gbrick_tab, std::max<size_t>(gbrick_tab.size(), 1) * 4) == hipSuccess;
-    ok = ok && hipMemcpy(m->d_grid, tab.data(), grid_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(m->d_bricks, bricks.data(), bricks.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(m->d_wfrag, wf.data(), wf.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
-         (brick_tab.empty() || hipMemcpy(m->d_brick_tab, brick_tab.data(), brick_tab.size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-         (gbrick_tab.empty() || hipMemcpy(m->d_gbrick_tab, gbrick_tab.data(), gbrick_tab.size() * 4, hipMemcpyHostToDevice) == hipSuccess);
-    if (!ok) {
-        d2r_nerf_destroy(m);
-        return d2r_fail(ctx, D2R_ERR_MEMORY, "device allocation/upload failed for the NeRF model");
-    }
-    P.grid = (const uint32_t *)m->d_grid;
+    if (grid_bytes >= (1ull << 32)) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "grid larger than 4 GiB");
+    const char *what = "the NeRF model";
+    int rc;
+    if ((rc = m->d_grid.alloc(ctx, grid_bytes, what)) || (rc = m->d_bricks.alloc(ctx, bricks.size() * 8, what)) ||
+        (rc = m->d_wfrag.alloc(ctx, wf.size() * 2, what)) || (rc = m->d_brick_tab.alloc(ctx, brick_tab.size() * 4, what)) ||
+        (rc = m->d_gbrick_tab.alloc(ctx, gbrick_tab.size() * 4, what)))
+        return rc;
+    D2R_HIP(ctx, hipMemcpy(m->d_grid.get(), tab.data(), grid_bytes, hipMemcpyHostToDevice));
+    D2R_HIP(ctx, hipMemcpy(m->d_bricks.get(), bricks.data(), bricks.size() * 8, hipMemcpyHostToDevice));
+    D2R_HIP(ctx, hipMemcpy(m->d_wfrag.get(), wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
+    if (!brick_tab.empty()) D2R_HIP(ctx, hipMemcpy(m->d_brick_tab.get(), brick_tab.data(), brick_tab.size() * 4, hipMemcpyHostToDevice));
+    if (!gbrick_tab.empty()) D2R_HIP(ctx, hipMemcpy(m->d_gbrick_tab.get(), gbrick_tab.data(), gbrick_tab.size() * 4, hipMemcpyHostToDevice));
+    P.grid = m->d_grid.get();
     P.grid_bytes = (uint32_t)grid_bytes;
-    P.bricks = (const uint64_t *)m->d_bricks;
-    P.wfrag = (const uint4 *)m->d_wfrag;
+    P.bricks = m->d_bricks.get();
+    P.wfrag = m->d_wfrag.get();
     P.wfrag16 = P.wfrag + (size_t)D2R_N_WFRAG * 64;
-    P.brick_tab = (const uint32_t *)m->d_brick_tab;
-    P.gbrick_tab = (const uint32_t *)m->d_gbrick_tab;
+    P.brick_tab = m->d_brick_tab.get();
+    P.gbrick_tab = m->d_gbrick_tab.get();
     P.gbrick_bytes = (uint32_t)(std::max<size_t>(gbrick_tab.size(), 1) * 4);
-    *out = m;
+    *out = m.release();
     return D2R_OK;
 }
 
 void d2r_nerf_destroy(d2r_nerf *m)
 {
     if (!m) return;
-    if (m->d_grid) hipFree(m->d_grid);
-    if (m->d_bricks) hipFree(m->d_bricks);
-    if (m->d_wfrag) hipFree(m->d_wfrag);
-    if (m->d_brick_tab) hipFree(m->d_brick_tab);
-    if (m->d_gbrick_tab) hipFree(m->d_gbrick_tab);
+    (void)hipSetDevice(m->device);
     delete m;
 }
 

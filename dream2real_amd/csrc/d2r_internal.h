@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/d2r.h"
+#include "d2r_shared.h"
 
 class D2rJobPool;   // pngio.h
 struct D2rPngBase;  // pngio.h
@@ -208,8 +209,11 @@ enum { D2R_T_MARCH = 0, D2R_T_RAYGEN = 1, D2R_T_CLIP = 2, D2R_T_PREP = 3, D2R_T_
 
 struct d2r_nerf {
     d2r_ctx *ctx;
+    int device = 0;
     NerfParams P{};
-    void *d_grid = nullptr, *d_bricks = nullptr, *d_wfrag = nullptr, *d_brick_tab = nullptr, *d_gbrick_tab = nullptr;
+    D2rDev<uint32_t> d_grid, d_brick_tab, d_gbrick_tab;
+    D2rDev<uint64_t> d_bricks;
+    D2rDev<uint4> d_wfrag;
 };
 
 // hipFuncSetAttribute once per (kernel instantiation, device), safe when different contexts are driven from
@@ -220,7 +224,6 @@ struct PerDeviceOnce {
     void run(int device, F &&fn) { std::call_once(flag[device % D2R_MAX_DEVICES], fn); }
 };
 
-int d2r_fail(d2r_ctx *ctx, int code, const std::string &msg);
 int d2r_reserve(d2r_ctx *ctx, d2r_ctx::Buf &b, size_t bytes);
 
 // phys.hip: the host side the two physics pre-filters (hulls + GJK in phys.hip, points against the TSDF field in sdfphys.hip) share

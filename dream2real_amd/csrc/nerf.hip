@@ -746,54 +746,15 @@ __global__ __launch_bounds__(256) void k_sort_count(const uint2 *__restrict__ qu
 // one block per bin: exclusive scan of its row of chunk counts, the row's total to bin_total
 __global__ __launch_bounds__(256) void k_sort_scan_rows(const uint32_t *__restrict__ qcount, uint32_t *__restrict__ counts, uint32_t *__restrict__ bin_total)
 {
-    __shared__ uint32_t part[256];
     const uint32_t n = *qcount, nchunks = (n + D2R_SORT_CHUNK - 1) / D2R_SORT_CHUNK;
     uint32_t *row = counts + (size_t)blockIdx.x * nchunks;
-    const uint32_t per = (nchunks + 255) / 256, lo = min(nchunks, threadIdx.x * per), hi = min(nchunks, lo + per);
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; i++) sum += row[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int i = 0; i < 256; i++) {
-            const uint32_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        bin_total[blockIdx.x] = run;
-    }
-    __syncthreads();
-    uint32_t run = part[threadIdx.x];
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint32_t v = row[i];
-        row[i] = run;
-        run += v;
-    }
+    const uint32_t total = d2r_block_scan_row(row, row, nchunks);
+    if (threadIdx.x == 0) bin_total[blockIdx.x] = total;
 }
 // exclusive scan of the bin totals (one block)
 __global__ __launch_bounds__(256) void k_sort_scan_bins(const uint32_t *__restrict__ bin_total, uint32_t *__restrict__ bin_base)
 {
-    __shared__ uint32_t part[256];
-    constexpr uint32_t PER = D2R_SORT_BINS / 256;
-    uint32_t sum = 0;
-    for (uint32_t i = 0; i < PER; i++) sum += bin_total[threadIdx.x * PER + i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int i = 0; i < 256; i++) {
-            const uint32_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    uint32_t run = part[threadIdx.x];
-    for (uint32_t i = 0; i < PER; i++) {
-        bin_base[threadIdx.x * PER + i] = run;
-        run += bin_total[threadIdx.x * PER + i];
-    }
+    d2r_block_scan_row(bin_total, bin_base, D2R_SORT_BINS);
 }
 __global__ __launch_bounds__(256) void k_sort_scatter(const uint2 *__restrict__ queue, const uint32_t *__restrict__ qcount, const uint32_t *__restrict__ counts,
                                                       const uint32_t *__restrict__ bin_base, uint2 *__restrict__ sorted)

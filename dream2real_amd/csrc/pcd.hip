@@ -21,8 +21,8 @@
 struct d2r_pcd {
     int device = 0;
     uint32_t n = 0;
-    float4 *xyz = nullptr;       // [n] (x, y, z, 0)
-    uint32_t *rgb = nullptr;     // [n] r | g << 8 | b << 16
+    D2rDev<float4> xyz;          // [n] (x, y, z, 0)
+    D2rDev<uint32_t> rgb;        // [n] r | g << 8 | b << 16
 };
 
 namespace {
@@ -190,13 +190,10 @@ __global__ __launch_bounds__(PCD_THREADS) void k_pcd_candidates(const float4 *__
 
 // ------------------------------------------------------------------------------------------------ host side
 
-// rigid inverse [R^T | -R^T t] of a row-major 4x4, fp64, fixed order
-void rigid_inverse(const double T[16], double out[16])
+// d2r_rigid_inverse as a 4x4 for mul4
+void rigid_inverse4(const float *T, double out[16])
 {
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) out[i * 4 + j] = T[j * 4 + i];
-        out[i * 4 + 3] = -((T[0 * 4 + i] * T[3] + T[1 * 4 + i] * T[7]) + T[2 * 4 + i] * T[11]);
-    }
+    d2r_rigid_inverse(T, out);
     out[12] = out[13] = out[14] = 0.0;
     out[15] = 1.0;
 }
@@ -250,11 +247,9 @@ int pcd_prepare(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const d2r_pc
     if ((uint64_t)bg->n + mv->n >= 0xffffffffull)
         return d2r_fail(ctx, D2R_ERR_INVALID, "background + movable points must stay below 2^32 - 1");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    double C4[16], O4[16], Ci[16], Oi[16], P[16], T[16], M[16];
-    load16(cam_pose, C4);
-    load16(obj_pose_now, O4);
-    rigid_inverse(C4, Ci);
-    rigid_inverse(O4, Oi);
+    double Ci[16], Oi[16], P[16], T[16], M[16];
+    rigid_inverse4(cam_pose, Ci);
+    rigid_inverse4(obj_pose_now, Oi);
     std::vector<PcdMat> mats(std::max<uint32_t>(K, 1));
     for (uint32_t k = 0; k < K; ++k) {
         load16(obj_poses + (size_t)k * 16, P);
@@ -267,13 +262,13 @@ int pcd_prepare(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const d2r_pc
     if ((rc = d2r_reserve(ctx, ctx->pcd_bg_keys, px * 8))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->pcd_bg_frame, px * 3))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->pcd_cols, ((size_t)bg->n + mv->n) * 4 + 4))) return rc;
-    D2R_HIP(ctx, hipMemcpyAsync(ctx->pcd_cols.p, bg->rgb, (size_t)bg->n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync((uint32_t *)ctx->pcd_cols.p + bg->n, mv->rgb, (size_t)mv->n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(ctx->pcd_cols.p, bg->rgb.get(), (size_t)bg->n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync((uint32_t *)ctx->pcd_cols.p + bg->n, mv->rgb.get(), (size_t)mv->n * 4, hipMemcpyDeviceToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(ctx->pcd_mats.p, mats.data(), (size_t)K * sizeof(PcdMat), hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemsetAsync(ctx->pcd_bg_keys.p, 0xff, px * 8, ctx->stream));
     if (bg->n)
         hipLaunchKernelGGL(k_pcd_splat_bg, dim3((bg->n + PCD_THREADS - 1) / PCD_THREADS), dim3(PCD_THREADS), 0, ctx->stream,
-                           bg->xyz, bg->n, to_mat34(Ci), c, (unsigned long long *)ctx->pcd_bg_keys.p);
+                           bg->xyz.get(), bg->n, to_mat34(Ci), c, (unsigned long long *)ctx->pcd_bg_keys.p);
     hipLaunchKernelGGL(k_pcd_resolve_bg, dim3((uint32_t)((px + PCD_THREADS - 1) / PCD_THREADS)), dim3(PCD_THREADS), 0, ctx->stream,
                        (const unsigned long long *)ctx->pcd_bg_keys.p, (uint32_t)px, (const uint32_t *)ctx->pcd_cols.p,
                        (uint8_t *)ctx->pcd_bg_frame.p);
@@ -285,7 +280,7 @@ int pcd_prepare(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const d2r_pc
 // candidates k0 .. k0 + nc - 1 -> ctx->frames [nc][H][W][3] (reserved by the caller for its largest pass)
 int pcd_candidates(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const PcdCam &c, uint32_t k0, uint32_t nc)
 {
-    hipLaunchKernelGGL(k_pcd_candidates, dim3(nc), dim3(PCD_THREADS), 0, ctx->stream, mv->xyz, mv->n, bg->n, (const uint32_t *)ctx->pcd_cols.p,
+    hipLaunchKernelGGL(k_pcd_candidates, dim3(nc), dim3(PCD_THREADS), 0, ctx->stream, mv->xyz.get(), mv->n, bg->n, (const uint32_t *)ctx->pcd_cols.p,
                        (const PcdMat *)ctx->pcd_mats.p + k0, c, (const unsigned long long *)ctx->pcd_bg_keys.p,
                        (const uint8_t *)ctx->pcd_bg_frame.p, (uint8_t *)ctx->frames.p);
     D2R_HIP(ctx, hipGetLastError());
@@ -307,20 +302,14 @@ int d2r_pcd_create(d2r_ctx *ctx, const float *xyz, const uint8_t *rgb, uint32_t 
         p[i] = float4{xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.f};
         col[i] = (uint32_t)rgb[3 * (size_t)i] | (uint32_t)rgb[3 * (size_t)i + 1] << 8 | (uint32_t)rgb[3 * (size_t)i + 2] << 16;
     }
-    d2r_pcd *m = new d2r_pcd;
+    std::unique_ptr<d2r_pcd> m(new d2r_pcd);
     m->device = ctx->device;
     m->n = n;
-    if (hipMalloc((void **)&m->xyz, p.size() * sizeof(float4)) != hipSuccess ||
-        hipMalloc((void **)&m->rgb, col.size() * 4) != hipSuccess) {
-        d2r_pcd_destroy(m);
-        return d2r_fail(ctx, D2R_ERR_MEMORY, "hipMalloc failed for a point cloud");
-    }
-    if (hipMemcpy(m->xyz, p.data(), p.size() * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->rgb, col.data(), col.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        d2r_pcd_destroy(m);
-        return d2r_fail(ctx, D2R_ERR_DEVICE, "hipMemcpy failed for a point cloud");
-    }
-    *out = m;
+    int rc;
+    if ((rc = m->xyz.alloc(ctx, p.size() * sizeof(float4), "a point cloud")) || (rc = m->rgb.alloc(ctx, col.size() * 4, "a point cloud"))) return rc;
+    D2R_HIP(ctx, hipMemcpy(m->xyz.get(), p.data(), p.size() * sizeof(float4), hipMemcpyHostToDevice));
+    D2R_HIP(ctx, hipMemcpy(m->rgb.get(), col.data(), col.size() * 4, hipMemcpyHostToDevice));
+    *out = m.release();
     return D2R_OK;
 }
 
@@ -328,8 +317,6 @@ void d2r_pcd_destroy(d2r_pcd *m)
 {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    if (m->xyz) (void)hipFree(m->xyz);
-    if (m->rgb) (void)hipFree(m->rgb);
     delete m;
 }
 

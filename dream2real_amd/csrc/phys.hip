@@ -22,13 +22,14 @@
 
 struct d2r_phys {
     d2r_ctx *ctx;
-    float *d_mov = nullptr;        // movable object's hull vertices (one or several convex parts, concatenated), world frame at the object's initial pose
-    uint32_t *d_moff = nullptr;    // [n_mov + 1] first vertex of each movable hull
+    int device = 0;
+    D2rDev<float> d_mov;           // movable object's hull vertices (one or several convex parts, concatenated), world frame at the object's initial pose
+    D2rDev<uint32_t> d_moff;       // [n_mov + 1] first vertex of each movable hull
     uint32_t n_mov = 0, n_mov_verts = 0;
-    float *d_stat = nullptr;       // static hull vertices, concatenated
-    uint32_t *d_off = nullptr;     // [n_stat + 1] first vertex of each static hull
+    D2rDev<float> d_stat;          // static hull vertices, concatenated
+    D2rDev<uint32_t> d_off;        // [n_stat + 1] first vertex of each static hull
     uint32_t n_stat = 0, n_stat_verts = 0;
-    float *d_stat_box = nullptr;   // [n_stat][6] axis-aligned box of each static hull (lo xyz, hi xyz)
+    D2rDev<float> d_stat_box;      // [n_stat][6] axis-aligned box of each static hull (lo xyz, hi xyz)
 };
 
 struct PhysKernelParams {
@@ -374,19 +375,21 @@ int d2r_phys_create(d2r_ctx *ctx, const float *movable_verts, const uint32_t *mo
     for (uint32_t h = 0; h < n_static; h++)
         if (static_offsets[h + 1] <= static_offsets[h]) return d2r_fail(ctx, D2R_ERR_INVALID, "static hull offsets must increase");
     (void)hipSetDevice(ctx->device);
-    d2r_phys *p = new (std::nothrow) d2r_phys();
+    std::unique_ptr<d2r_phys> p(new (std::nothrow) d2r_phys());
     if (!p) return d2r_fail(ctx, D2R_ERR_MEMORY, "out of host memory");
     p->ctx = ctx;
+    p->device = ctx->device;
     p->n_mov = n_movable;
     p->n_mov_verts = movable_offsets[n_movable];
     p->n_stat = n_static;
     p->n_stat_verts = n_static ? static_offsets[n_static] : 0;
     const uint32_t zero = 0;
-    bool ok = hipMalloc(&p->d_mov, (size_t)p->n_mov_verts * 12) == hipSuccess &&
-              hipMalloc(&p->d_moff, ((size_t)n_movable + 1) * 4) == hipSuccess &&
-              hipMalloc(&p->d_stat, std::max<size_t>(1, (size_t)p->n_stat_verts * 12)) == hipSuccess &&
-              hipMalloc(&p->d_off, ((size_t)n_static + 1) * 4) == hipSuccess &&
-              hipMalloc(&p->d_stat_box, std::max<size_t>(1, (size_t)n_static) * 24) == hipSuccess;
+    const char *what = "the physics shapes";
+    int rc;
+    if ((rc = p->d_mov.alloc(ctx, (size_t)p->n_mov_verts * 12, what)) || (rc = p->d_moff.alloc(ctx, ((size_t)n_movable + 1) * 4, what)) ||
+        (rc = p->d_stat.alloc(ctx, (size_t)p->n_stat_verts * 12, what)) || (rc = p->d_off.alloc(ctx, ((size_t)n_static + 1) * 4, what)) ||
+        (rc = p->d_stat_box.alloc(ctx, (size_t)std::max<uint32_t>(1, n_static) * 24, what)))
+        return rc;
     std::vector<float> boxes((size_t)std::max<uint32_t>(1, n_static) * 6, 0.f);
     for (uint32_t h = 0; h < n_static; h++)
         for (int k = 0; k < 3; k++) {
@@ -398,27 +401,19 @@ int d2r_phys_create(d2r_ctx *ctx, const float *movable_verts, const uint32_t *mo
             boxes[6 * (size_t)h + k] = lo;
             boxes[6 * (size_t)h + 3 + k] = hi;
         }
-    ok = ok && hipMemcpy(p->d_mov, movable_verts, (size_t)p->n_mov_verts * 12, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_moff, movable_offsets, ((size_t)n_movable + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         (p->n_stat_verts == 0 || hipMemcpy(p->d_stat, static_verts, (size_t)p->n_stat_verts * 12, hipMemcpyHostToDevice) == hipSuccess) &&
-         hipMemcpy(p->d_off, n_static ? static_offsets : &zero, ((size_t)n_static + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_stat_box, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        d2r_phys_destroy(p);
-        return d2r_fail(ctx, D2R_ERR_MEMORY, "device allocation/upload failed for the physics shapes");
-    }
-    *out = p;
+    D2R_HIP(ctx, hipMemcpy(p->d_mov.get(), movable_verts, (size_t)p->n_mov_verts * 12, hipMemcpyHostToDevice));
+    D2R_HIP(ctx, hipMemcpy(p->d_moff.get(), movable_offsets, ((size_t)n_movable + 1) * 4, hipMemcpyHostToDevice));
+    if (p->n_stat_verts) D2R_HIP(ctx, hipMemcpy(p->d_stat.get(), static_verts, (size_t)p->n_stat_verts * 12, hipMemcpyHostToDevice));
+    D2R_HIP(ctx, hipMemcpy(p->d_off.get(), n_static ? static_offsets : &zero, ((size_t)n_static + 1) * 4, hipMemcpyHostToDevice));
+    D2R_HIP(ctx, hipMemcpy(p->d_stat_box.get(), boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice));
+    *out = p.release();
     return D2R_OK;
 }
 
 void d2r_phys_destroy(d2r_phys *p)
 {
     if (!p) return;
-    if (p->d_mov) (void)hipFree(p->d_mov);
-    if (p->d_moff) (void)hipFree(p->d_moff);
-    if (p->d_stat) (void)hipFree(p->d_stat);
-    if (p->d_off) (void)hipFree(p->d_off);
-    if (p->d_stat_box) (void)hipFree(p->d_stat_box);
+    (void)hipSetDevice(p->device);
     delete p;
 }
 
@@ -476,8 +471,8 @@ int d2r_phys_check(d2r_ctx *ctx, const d2r_phys *phys, const d2r_phys_params *pr
     D2R_HIP(ctx, hipMemcpyAsync(d_valid, valid_io, N, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(d_mask, mask.data(), oris, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_phys_check, dim3((N + 3) / 4), dim3(256), 0, ctx->stream, P, (const float *)ctx->poses.p, N,
-                       (const uint8_t *)d_mask, (const float *)phys->d_mov, (const uint32_t *)phys->d_moff, phys->n_mov, (const float *)phys->d_stat,
-                       (const uint32_t *)phys->d_off, phys->n_stat, (const float *)phys->d_stat_box, d_valid);
+                       (const uint8_t *)d_mask, (const float *)phys->d_mov.get(), (const uint32_t *)phys->d_moff.get(), phys->n_mov,
+                       (const float *)phys->d_stat.get(), (const uint32_t *)phys->d_off.get(), phys->n_stat, (const float *)phys->d_stat_box.get(), d_valid);
     D2R_HIP(ctx, hipGetLastError());
     D2R_HIP(ctx, hipMemcpyAsync(valid_io, d_valid, N, hipMemcpyDeviceToHost, ctx->stream));
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));

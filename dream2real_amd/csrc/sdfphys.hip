@@ -33,12 +33,17 @@ struct d2r_sdfphys {
     d2r_ctx *ctx = nullptr;
     int device = 0;
     SdfGrid G{};
-    uint32_t *d_words = nullptr;    // [nz][ny][wpr] touch bits, all static grids ORed
-    uint32_t *d_coarse = nullptr;   // [ceil(blocks / 32)] bit (bz ncby + by) ncbx + bx
-    float *d_pts = nullptr;         // [3][n_points] x, y, z of the movable points (SoA), world frame at the initial pose
+    D2rDev<uint32_t> d_words;       // [nz][ny][wpr] touch bits, all static grids ORed
+    D2rDev<uint32_t> d_coarse;      // [ceil(blocks / 32)] bit (bz ncby + by) ncbx + bx
+    D2rDev<float> d_pts;            // [3][n_points] x, y, z of the movable points (SoA), world frame at the initial pose
     uint32_t n_points = 0;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // upload / kernel / download boundaries of the last check
     bool timed = false;
+    ~d2r_sdfphys()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 struct SdfCheckParams {
@@ -158,12 +163,6 @@ __global__ __launch_bounds__(SDF_THREADS) void k_sdf_check(SdfCheckParams P, Sdf
     if (lane == 0) valid[pose] = ok ? 1 : 0;
 }
 
-int sdf_fail(d2r_sdfphys *h, d2r_ctx *ctx, int code, const char *msg)
-{
-    if (h) d2r_sdfphys_destroy(h);
-    return d2r_fail(ctx, code, msg);
-}
-
 }  // namespace
 
 extern "C" {
@@ -204,26 +203,25 @@ int d2r_sdfphys_create(d2r_ctx *ctx, const int32_t *b0, const uint32_t *nv, floa
     for (uint32_t i = 0; i < n_points; ++i)
         for (int a = 0; a < 3; ++a) soa[(size_t)a * n_points + i] = points[(size_t)i * 3 + a];
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    d2r_sdfphys *h = new (std::nothrow) d2r_sdfphys();
+    std::unique_ptr<d2r_sdfphys> h(new (std::nothrow) d2r_sdfphys());
     if (!h) return d2r_fail(ctx, D2R_ERR_MEMORY, "out of host memory");
     h->ctx = ctx;
     h->device = ctx->device;
     h->G = G;
     h->n_points = n_points;
-    bool ok = hipMalloc(&h->d_words, n_words * 4) == hipSuccess && hipMalloc(&h->d_coarse, (size_t)n_cwords * 4) == hipSuccess &&
-              hipMalloc(&h->d_pts, soa.size() * 4) == hipSuccess;
-    for (int k = 0; k < 4 && ok; ++k) ok = hipEventCreate(&h->ev[k]) == hipSuccess;
-    if (!ok) return sdf_fail(h, ctx, D2R_ERR_MEMORY, "device allocation failed for the physics field");
-    ok = hipMemcpyAsync(h->d_words, field.data(), n_words * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-         hipMemcpyAsync(h->d_pts, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(k_sdf_coarse, dim3((n_cwords + 3) / 4), dim3(SDF_THREADS), 0, ctx->stream, (const uint32_t *)h->d_words, G, n_blocks,
-                           n_cwords, h->d_coarse);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    ok = hipStreamSynchronize(ctx->stream) == hipSuccess && ok;       // field and soa (host memory of this call) have been consumed
-    if (!ok) return sdf_fail(h, ctx, D2R_ERR_DEVICE, "upload failed for the physics field");
-    *out = h;
+    D2rDrain drain{ctx->stream};      // field and soa (host memory of this call) have been consumed, whichever return is taken
+    int rc;
+    if ((rc = h->d_words.alloc(ctx, n_words * 4, "the physics field")) || (rc = h->d_coarse.alloc(ctx, (size_t)n_cwords * 4, "the physics field")) ||
+        (rc = h->d_pts.alloc(ctx, soa.size() * 4, "the physics field")))
+        return rc;
+    for (int k = 0; k < 4; ++k) D2R_HIP(ctx, hipEventCreate(&h->ev[k]));
+    D2R_HIP(ctx, hipMemcpyAsync(h->d_words.get(), field.data(), n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(h->d_pts.get(), soa.data(), soa.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_sdf_coarse, dim3((n_cwords + 3) / 4), dim3(SDF_THREADS), 0, ctx->stream, (const uint32_t *)h->d_words.get(), G, n_blocks,
+                       n_cwords, h->d_coarse.get());
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *out = h.release();
     return D2R_OK;
 }
 
@@ -231,10 +229,6 @@ void d2r_sdfphys_destroy(d2r_sdfphys *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    for (void *p : {(void *)h->d_words, (void *)h->d_coarse, (void *)h->d_pts})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
     delete h;
 }
 
@@ -244,7 +238,7 @@ int d2r_sdfphys_check(d2r_ctx *ctx, d2r_sdfphys *h, const d2r_phys_params *prm, 
     uint64_t oris = 1;
     if (int rc = d2r_phys_orientations(ctx, prm, N, &oris)) return rc;
     SdfCheckParams P;
-    // inv(init_pose) as the rigid inverse [R^T | -R^T t] in fp64, fixed order (tsdf.hip, pcd.hip)
+    // init_pose must be rigid to 1e-3 for its inverse to be [R^T | -R^T t]
     const float *I = prm->init_pose;
     double dev = 0.0;
     for (int i = 0; i < 3; ++i)
@@ -255,10 +249,7 @@ int d2r_sdfphys_check(d2r_ctx *ctx, d2r_sdfphys *h, const d2r_phys_params *prm, 
         }
     if (!(dev <= 1e-3) || I[12] != 0.f || I[13] != 0.f || I[14] != 0.f || I[15] != 1.f)
         return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_sdfphys_check: init_pose must be a rigid transform");
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) P.inv[i * 4 + j] = (double)I[j * 4 + i];
-        P.inv[i * 4 + 3] = -(((double)I[0 * 4 + i] * (double)I[3] + (double)I[1 * 4 + i] * (double)I[7]) + (double)I[2 * 4 + i] * (double)I[11]);
-    }
+    d2r_rigid_inverse(I, P.inv);
     P.table_z = prm->table_z;
     for (int i = 0; i < 3; i++) P.drop[i] = prm->unsup_thresh * prm->gravity[i];
     P.perturb = prm->perturb;
@@ -276,7 +267,7 @@ int d2r_sdfphys_check(d2r_ctx *ctx, d2r_sdfphys *h, const d2r_phys_params *prm, 
     D2R_HIP(ctx, hipMemcpyAsync(d_mask, mask.data(), oris, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipEventRecord(h->ev[1], ctx->stream));
     hipLaunchKernelGGL(k_sdf_check, dim3((N + 3) / 4), dim3(SDF_THREADS), 0, ctx->stream, P, h->G, (const float *)ctx->poses.p, N,
-                       (const uint8_t *)d_mask, (const uint32_t *)h->d_words, (const uint32_t *)h->d_coarse, (const float *)h->d_pts, h->n_points,
+                       (const uint8_t *)d_mask, (const uint32_t *)h->d_words.get(), (const uint32_t *)h->d_coarse.get(), (const float *)h->d_pts.get(), h->n_points,
                        d_valid);
     D2R_HIP(ctx, hipGetLastError());
     D2R_HIP(ctx, hipEventRecord(h->ev[2], ctx->stream));

@@ -49,13 +49,18 @@ struct d2r_tsdf {
     TsdfGrid G{};
     uint64_t n_vox = 0;
     uint32_t n_blocks = 0;
-    float2 *vox = nullptr;          // [nz][ny][nx] (tsdf, weight)
-    uint32_t *stamp = nullptr;      // [n_blocks] 1 + index of the last frame that touched the block
-    uint8_t *ever = nullptr;        // [n_blocks]
-    uint32_t *list = nullptr;       // [n_blocks] blocks of the current frame (order does not matter: voxels are independent)
-    uint32_t *counters = nullptr;   // [0] length of list, [1] valid pixels of the frame, [2..3] vertex / triangle totals, [4] solid voxels
+    D2rDev<float2> vox;             // [nz][ny][nx] (tsdf, weight)
+    D2rDev<uint32_t> stamp;         // [n_blocks] 1 + index of the last frame that touched the block
+    D2rDev<uint8_t> ever;           // [n_blocks]
+    D2rDev<uint32_t> list;          // [n_blocks] blocks of the current frame (order does not matter: voxels are independent)
+    D2rDev<uint32_t> counters;      // [0] length of list, [1] valid pixels of the frame, [2..3] vertex / triangle totals, [4] solid voxels
     uint32_t frame = 0;
     d2r_ctx::Buf depth_in, mask_in, zbuf;
+    ~d2r_tsdf()
+    {
+        for (void *p : {depth_in.p, mask_in.p, zbuf.p})
+            if (p) (void)hipFree(p);
+    }
     // the last extraction, kept for the fill call
     bool have = false;
     float key[9] = {};
@@ -64,7 +69,7 @@ struct d2r_tsdf {
 
 namespace {
 
-constexpr uint32_t TSDF_THREADS = 256;
+constexpr uint32_t TSDF_THREADS = D2R_SCAN_THREADS;
 constexpr int ER_TW = 64, ER_TH = 32;        // output tile of k_erode
 constexpr uint32_t MC_CHUNK = 4096;          // voxels per scan chunk: 256 threads x 16
 
@@ -297,49 +302,17 @@ __device__ __forceinline__ uint2 mc_counts16(const uint8_t *ebits, uint64_t firs
 // (vertices, triangles) of each 4096-voxel chunk; the grid is whole blocks, so chunks are whole
 __global__ __launch_bounds__(TSDF_THREADS) void k_mc_chunk_sums(const uint8_t *__restrict__ ebits, uint2 *__restrict__ chunk)
 {
-    __shared__ uint2 part[TSDF_THREADS];
-    part[threadIdx.x] = mc_counts16(ebits, (uint64_t)blockIdx.x * MC_CHUNK + threadIdx.x * 16u);
-    __syncthreads();
-    for (uint32_t s = TSDF_THREADS / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            part[threadIdx.x].x += part[threadIdx.x + s].x;
-            part[threadIdx.x].y += part[threadIdx.x + s].y;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) chunk[blockIdx.x] = part[0];
+    const uint2 sum = d2r_block_sum(mc_counts16(ebits, (uint64_t)blockIdx.x * MC_CHUNK + threadIdx.x * 16u));
+    if (threadIdx.x == 0) chunk[blockIdx.x] = sum;
 }
 
-// exclusive scan of the chunk sums in place (one workgroup, the shape of k_sort_scan_rows); totals to counters[2..3]
+// exclusive scan of the chunk sums in place (one workgroup); totals to counters[2..3]
 __global__ __launch_bounds__(TSDF_THREADS) void k_mc_scan_chunks(uint2 *__restrict__ chunk, uint32_t nchunks, uint32_t *__restrict__ counters)
 {
-    __shared__ uint2 part[TSDF_THREADS];
-    const uint32_t per = (nchunks + TSDF_THREADS - 1) / TSDF_THREADS, lo = min(nchunks, threadIdx.x * per), hi = min(nchunks, lo + per);
-    uint2 sum = make_uint2(0, 0);
-    for (uint32_t i = lo; i < hi; i++) {
-        sum.x += chunk[i].x;
-        sum.y += chunk[i].y;
-    }
-    part[threadIdx.x] = sum;
-    __syncthreads();
+    const uint2 total = d2r_block_scan_row(chunk, chunk, nchunks);
     if (threadIdx.x == 0) {
-        uint2 run = make_uint2(0, 0);
-        for (uint32_t i = 0; i < TSDF_THREADS; i++) {
-            const uint2 v = part[i];
-            part[i] = run;
-            run.x += v.x;
-            run.y += v.y;
-        }
-        counters[2] = run.x;
-        counters[3] = run.y;
-    }
-    __syncthreads();
-    uint2 run = part[threadIdx.x];
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint2 v = chunk[i];
-        chunk[i] = run;
-        run.x += v.x;
-        run.y += v.y;
+        counters[2] = total.x;
+        counters[3] = total.y;
     }
 }
 
@@ -351,22 +324,11 @@ __global__ __launch_bounds__(TSDF_THREADS) void k_mc_emit(const float2 *__restri
                                                           uint32_t *__restrict__ vbase, float *__restrict__ verts, uint32_t n_verts,
                                                           uint32_t *__restrict__ tris, uint32_t n_tris)
 {
-    __shared__ uint32_t part[TSDF_THREADS];
     const uint64_t first = (uint64_t)blockIdx.x * MC_CHUNK + threadIdx.x * 16u;
-    const uint2 mine = mc_counts16(ebits, first);
-    part[threadIdx.x] = TRIS ? mine.y : mine.x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = TRIS ? chunk[blockIdx.x].y : chunk[blockIdx.x].x;
-        for (uint32_t i = 0; i < TSDF_THREADS; i++) {
-            const uint32_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    if ((TRIS ? mine.y : mine.x) == 0) return;
-    uint32_t run = part[threadIdx.x];
+    const uint2 both = mc_counts16(ebits, first);
+    const uint32_t mine = TRIS ? both.y : both.x;
+    uint32_t run = d2r_block_scan(mine, TRIS ? chunk[blockIdx.x].y : chunk[blockIdx.x].x);
+    if (mine == 0) return;
     const size_t st[3] = {1, G.nv[0], (size_t)G.nv[0] * G.nv[1]};
     for (uint32_t k = 0; k < 16; ++k) {
         const uint64_t i = first + k;
@@ -447,41 +409,15 @@ __device__ __forceinline__ uint32_t solid_mask16(const float2 *__restrict__ vox,
 
 __global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_solid_count(const float2 *__restrict__ vox, float thr, uint32_t *__restrict__ chunk)
 {
-    __shared__ uint32_t part[TSDF_THREADS];
-    part[threadIdx.x] = (uint32_t)__popc(solid_mask16(vox, (uint64_t)blockIdx.x * MC_CHUNK, thr));
-    __syncthreads();
-    for (uint32_t s = TSDF_THREADS / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) chunk[blockIdx.x] = part[0];
+    const uint32_t sum = d2r_block_sum((uint32_t)__popc(solid_mask16(vox, (uint64_t)blockIdx.x * MC_CHUNK, thr)));
+    if (threadIdx.x == 0) chunk[blockIdx.x] = sum;
 }
 
-// exclusive scan of the chunk counts in place (one workgroup, the shape of k_mc_scan_chunks); the total to counters[4]
+// exclusive scan of the chunk counts in place (one workgroup); the total to counters[4]
 __global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_solid_scan(uint32_t *__restrict__ chunk, uint32_t nchunks, uint32_t *__restrict__ counters)
 {
-    __shared__ uint32_t part[TSDF_THREADS];
-    const uint32_t per = (nchunks + TSDF_THREADS - 1) / TSDF_THREADS, lo = min(nchunks, threadIdx.x * per), hi = min(nchunks, lo + per);
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; i++) sum += chunk[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (uint32_t i = 0; i < TSDF_THREADS; i++) {
-            const uint32_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        counters[4] = run;
-    }
-    __syncthreads();
-    uint32_t run = part[threadIdx.x];
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint32_t v = chunk[i];
-        chunk[i] = run;
-        run += v;
-    }
+    const uint32_t total = d2r_block_scan_row(chunk, chunk, nchunks);
+    if (threadIdx.x == 0) counters[4] = total;
 }
 
 // the centres (float)g * voxel of the solid voxels, in voxel order: a chunk's 16 steps x 4 waves are 64 runs of 64 voxels
@@ -523,29 +459,9 @@ __global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_solid_emit(const float2 *
 
 // ------------------------------------------------------------------------------------------------ host side
 
-// rigid inverse [R^T | -R^T t] of a row-major 4x4, fp64, fixed order (as pcd.hip composes its matrices)
-void tsdf_rigid_inverse(const float *T, float out[12])
-{
-    double t[16];
-    for (int i = 0; i < 16; ++i) t[i] = (double)T[i];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) out[i * 4 + j] = (float)t[j * 4 + i];
-        out[i * 4 + 3] = (float)(-((t[0 * 4 + i] * t[3] + t[1 * 4 + i] * t[7]) + t[2 * 4 + i] * t[11]));
-    }
-}
-
 int tsdf_fail(d2r_tsdf *v, int code, const std::string &msg) { return d2r_fail(v ? v->ctx : nullptr, code, msg); }
 
-template <class T>
-int tsdf_alloc(d2r_ctx *ctx, T *&p, size_t bytes, bool zero)
-{
-    if (hipMalloc((void **)&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
-        p = nullptr;
-        return d2r_fail(ctx, D2R_ERR_MEMORY, "hipMalloc failed for a TSDF volume (" + std::to_string(bytes >> 20) + " MiB)");
-    }
-    if (zero) D2R_HIP(ctx, hipMemset(p, 0, std::max<size_t>(bytes, 16)));
-    return D2R_OK;
-}
+constexpr const char *TSDF_MEM = "a TSDF volume";
 
 // the whole extraction on the device: raw vertices and triangles in canonical order to the host
 int tsdf_extract_raw(d2r_tsdf *v, float thr, std::vector<float> &verts, std::vector<uint32_t> &tris)
@@ -553,49 +469,42 @@ int tsdf_extract_raw(d2r_tsdf *v, float thr, std::vector<float> &verts, std::vec
     d2r_ctx *ctx = v->ctx;
     const uint64_t n = v->n_vox;
     const uint32_t nchunks = (uint32_t)(n / MC_CHUNK), nblk = (uint32_t)((n + TSDF_THREADS - 1) / TSDF_THREADS);
-    uint8_t *cubecase = nullptr, *ebits = nullptr;
-    uint32_t *vbase = nullptr, *d_tris = nullptr;
-    uint2 *chunk = nullptr;
-    float *d_verts = nullptr;
-    int rc = D2R_OK;
-    auto body = [&]() -> int {
-        int r;
-        if ((r = tsdf_alloc(ctx, cubecase, n, false)) || (r = tsdf_alloc(ctx, ebits, n, false)) || (r = tsdf_alloc(ctx, vbase, n * 4, false)) ||
-            (r = tsdf_alloc(ctx, chunk, (size_t)nchunks * 8, false)))
-            return r;
-        hipLaunchKernelGGL(k_mc_classify, dim3(nblk), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, v->ever, v->G, n, thr, cubecase);
-        hipLaunchKernelGGL(k_mc_edges, dim3(nblk), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, v->ever, cubecase, v->G, n, ebits);
-        hipLaunchKernelGGL(k_mc_chunk_sums, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, ebits, chunk);
-        hipLaunchKernelGGL(k_mc_scan_chunks, dim3(1), dim3(TSDF_THREADS), 0, ctx->stream, chunk, nchunks, v->counters);
-        D2R_HIP(ctx, hipGetLastError());
-        uint32_t tot[2] = {0, 0};
-        D2R_HIP(ctx, hipMemcpyAsync(tot, v->counters + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
-        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if ((uint64_t)tot[0] * 3 >= 0xffffffffull || (uint64_t)tot[1] * 3 >= 0xffffffffull)
-            return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "TSDF surface has too many vertices for 32-bit indices");
-        verts.resize((size_t)tot[0] * 3);
-        tris.resize((size_t)tot[1] * 3);
-        if (tot[0] == 0 || tot[1] == 0) {
-            verts.clear();
-            tris.clear();
-            return D2R_OK;
-        }
-        if ((r = tsdf_alloc(ctx, d_verts, verts.size() * 4, false)) || (r = tsdf_alloc(ctx, d_tris, tris.size() * 4, false))) return r;
-        hipLaunchKernelGGL(k_mc_emit<false>, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, cubecase, ebits, chunk, v->G, vbase, d_verts,
-                           tot[0], d_tris, tot[1]);
-        hipLaunchKernelGGL(k_mc_emit<true>, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, cubecase, ebits, chunk, v->G, vbase, d_verts,
-                           tot[0], d_tris, tot[1]);
-        D2R_HIP(ctx, hipGetLastError());
-        D2R_HIP(ctx, hipMemcpyAsync(verts.data(), d_verts, verts.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        D2R_HIP(ctx, hipMemcpyAsync(tris.data(), d_tris, tris.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    D2rDev<uint8_t> cubecase, ebits;
+    D2rDev<uint32_t> vbase, d_tris;
+    D2rDev<uint2> chunk;
+    D2rDev<float> d_verts;
+    D2rDrain drain{ctx->stream};
+    int r;
+    if ((r = cubecase.alloc(ctx, n, TSDF_MEM)) || (r = ebits.alloc(ctx, n, TSDF_MEM)) || (r = vbase.alloc(ctx, n * 4, TSDF_MEM)) ||
+        (r = chunk.alloc(ctx, (size_t)nchunks * 8, TSDF_MEM)))
+        return r;
+    hipLaunchKernelGGL(k_mc_classify, dim3(nblk), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), v->ever.get(), v->G, n, thr, cubecase.get());
+    hipLaunchKernelGGL(k_mc_edges, dim3(nblk), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), v->ever.get(), cubecase.get(), v->G, n, ebits.get());
+    hipLaunchKernelGGL(k_mc_chunk_sums, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, ebits.get(), chunk.get());
+    hipLaunchKernelGGL(k_mc_scan_chunks, dim3(1), dim3(TSDF_THREADS), 0, ctx->stream, chunk.get(), nchunks, v->counters.get());
+    D2R_HIP(ctx, hipGetLastError());
+    uint32_t tot[2] = {0, 0};
+    D2R_HIP(ctx, hipMemcpyAsync(tot, v->counters.get() + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((uint64_t)tot[0] * 3 >= 0xffffffffull || (uint64_t)tot[1] * 3 >= 0xffffffffull)
+        return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "TSDF surface has too many vertices for 32-bit indices");
+    verts.resize((size_t)tot[0] * 3);
+    tris.resize((size_t)tot[1] * 3);
+    if (tot[0] == 0 || tot[1] == 0) {
+        verts.clear();
+        tris.clear();
         return D2R_OK;
-    };
-    rc = body();
-    if (rc) (void)hipStreamSynchronize(ctx->stream);
-    for (void *p : {(void *)cubecase, (void *)ebits, (void *)vbase, (void *)chunk, (void *)d_verts, (void *)d_tris})
-        if (p) (void)hipFree(p);
-    return rc;
+    }
+    if ((r = d_verts.alloc(ctx, verts.size() * 4, TSDF_MEM)) || (r = d_tris.alloc(ctx, tris.size() * 4, TSDF_MEM))) return r;
+    hipLaunchKernelGGL(k_mc_emit<false>, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), cubecase.get(), ebits.get(), chunk.get(), v->G,
+                       vbase.get(), d_verts.get(), tot[0], d_tris.get(), tot[1]);
+    hipLaunchKernelGGL(k_mc_emit<true>, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), cubecase.get(), ebits.get(), chunk.get(), v->G,
+                       vbase.get(), d_verts.get(), tot[0], d_tris.get(), tot[1]);
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipMemcpyAsync(verts.data(), d_verts.get(), verts.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(tris.data(), d_tris.get(), tris.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return D2R_OK;
 }
 
 }  // namespace
@@ -634,20 +543,18 @@ int d2r_tsdf_create(d2r_ctx *ctx, const float *bounds, float voxel, float trunc,
         return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, msg);
     }
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    d2r_tsdf *v = new d2r_tsdf;
+    std::unique_ptr<d2r_tsdf> v(new d2r_tsdf);
     v->ctx = ctx;
     v->device = ctx->device;
     v->G = G;
     v->n_vox = (uint64_t)G.nv[0] * G.nv[1] * G.nv[2];
     v->n_blocks = G.nb[0] * G.nb[1] * G.nb[2];
     int rc;
-    if ((rc = tsdf_alloc(ctx, v->vox, v->n_vox * sizeof(float2), true)) || (rc = tsdf_alloc(ctx, v->stamp, (size_t)v->n_blocks * 4, true)) ||
-        (rc = tsdf_alloc(ctx, v->ever, v->n_blocks, true)) || (rc = tsdf_alloc(ctx, v->list, (size_t)v->n_blocks * 4, true)) ||
-        (rc = tsdf_alloc(ctx, v->counters, 64, true))) {
-        d2r_tsdf_destroy(v);
+    if ((rc = v->vox.alloc(ctx, v->n_vox * sizeof(float2), TSDF_MEM, true)) || (rc = v->stamp.alloc(ctx, (size_t)v->n_blocks * 4, TSDF_MEM, true)) ||
+        (rc = v->ever.alloc(ctx, v->n_blocks, TSDF_MEM, true)) || (rc = v->list.alloc(ctx, (size_t)v->n_blocks * 4, TSDF_MEM, true)) ||
+        (rc = v->counters.alloc(ctx, 64, TSDF_MEM, true)))
         return rc;
-    }
-    *out = v;
+    *out = v.release();
     return D2R_OK;
 }
 
@@ -655,8 +562,6 @@ void d2r_tsdf_destroy(d2r_tsdf *v)
 {
     if (!v) return;
     (void)hipSetDevice(v->device);
-    for (void *p : {(void *)v->vox, (void *)v->stamp, (void *)v->ever, (void *)v->list, (void *)v->counters, v->depth_in.p, v->mask_in.p, v->zbuf.p})
-        if (p) (void)hipFree(p);
     delete v;
 }
 
@@ -682,22 +587,24 @@ int d2r_tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *ma
     c.W = (int32_t)w;
     c.H = (int32_t)h;
     memcpy(c.m, cam_pose, sizeof c.m);
-    tsdf_rigid_inverse(cam_pose, c.inv);
+    double inv[12];
+    d2r_rigid_inverse(cam_pose, inv);
+    for (int i = 0; i < 12; ++i) c.inv[i] = (float)inv[i];
     const size_t px = (size_t)w * h;
     int rc;
     if ((rc = d2r_reserve(ctx, v->depth_in, px * 2)) || (rc = d2r_reserve(ctx, v->mask_in, px)) || (rc = d2r_reserve(ctx, v->zbuf, px * 4))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(v->depth_in.p, depth_u16, px * 2, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(v->mask_in.p, mask_u8, px, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemsetAsync(v->counters, 0, 8, ctx->stream));
+    D2R_HIP(ctx, hipMemsetAsync(v->counters.get(), 0, 8, ctx->stream));
     const uint32_t cur = ++v->frame;
     const int steps = (int)lrint((double)v->G.trunc / (double)v->G.voxel);
     hipLaunchKernelGGL(k_erode, dim3((w + ER_TW - 1) / ER_TW, (h + ER_TH - 1) / ER_TH), dim3(TSDF_THREADS), 0, ctx->stream,
                        (const uint16_t *)v->depth_in.p, (const uint8_t *)v->mask_in.p, (int)w, (int)h, (int)erode_k, 3.0f, (float *)v->zbuf.p,
-                       v->counters);
+                       v->counters.get());
     hipLaunchKernelGGL(k_mark_blocks, dim3((uint32_t)((px + TSDF_THREADS - 1) / TSDF_THREADS)), dim3(TSDF_THREADS), 0, ctx->stream,
-                       (const float *)v->zbuf.p, c, v->G, steps, cur, v->stamp, v->ever, v->list, v->counters);
+                       (const float *)v->zbuf.p, c, v->G, steps, cur, v->stamp.get(), v->ever.get(), v->list.get(), v->counters.get());
     const uint32_t grid = std::min<uint32_t>(v->n_blocks, (uint32_t)ctx->n_cu * 16u);
-    hipLaunchKernelGGL(k_integrate, dim3(grid), dim3(TSDF_THREADS), 0, ctx->stream, (const float *)v->zbuf.p, c, v->G, v->list, v->counters, v->vox);
+    hipLaunchKernelGGL(k_integrate, dim3(grid), dim3(TSDF_THREADS), 0, ctx->stream, (const float *)v->zbuf.p, c, v->G, v->list.get(), v->counters.get(), v->vox.get());
     D2R_HIP(ctx, hipGetLastError());
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the caller's frame (pageable host memory) has been consumed
     v->have = false;
@@ -710,7 +617,7 @@ int d2r_tsdf_read_voxels(d2r_tsdf *v, uint32_t *n_blocks, int32_t *block_coords,
     d2r_ctx *ctx = v->ctx;
     D2R_HIP(ctx, hipSetDevice(v->device));
     std::vector<uint8_t> ever(v->n_blocks);
-    D2R_HIP(ctx, hipMemcpyAsync(ever.data(), v->ever, v->n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(ever.data(), v->ever.get(), v->n_blocks, hipMemcpyDeviceToHost, ctx->stream));
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<uint32_t> blocks;
     for (uint32_t b = 0; b < v->n_blocks; ++b)
@@ -728,25 +635,19 @@ int d2r_tsdf_read_voxels(d2r_tsdf *v, uint32_t *n_blocks, int32_t *block_coords,
         block_coords[3 * k + 1] = G.b0[1] + (int32_t)((b / G.nb[0]) % G.nb[1]);
         block_coords[3 * k + 2] = G.b0[2] + (int32_t)(b / (G.nb[0] * G.nb[1]));
     }
-    uint32_t *d_blocks = nullptr;
-    float *d_t = nullptr, *d_w = nullptr;
+    D2rDev<uint32_t> d_blocks;
+    D2rDev<float> d_t, d_w;
+    D2rDrain drain{ctx->stream};
     const size_t nb = blocks.size(), bytes = nb * D2R_TSDF_BLOCK_VOX * 4;
     int rc;
-    if (!(rc = tsdf_alloc(ctx, d_blocks, nb * 4, false)) && !(rc = tsdf_alloc(ctx, d_t, bytes, false)) && !(rc = tsdf_alloc(ctx, d_w, bytes, false))) {
-        hipError_t e = hipMemcpyAsync(d_blocks, blocks.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_tsdf_gather, dim3((uint32_t)nb), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, G, d_blocks, d_t, d_w);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(tsdf, d_t, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(weight, d_w, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) rc = d2r_fail(ctx, D2R_ERR_DEVICE, std::string("d2r_tsdf_read_voxels: ") + hipGetErrorString(e));
-    }
-    for (void *p : {(void *)d_blocks, (void *)d_t, (void *)d_w})
-        if (p) (void)hipFree(p);
-    return rc;
+    if ((rc = d_blocks.alloc(ctx, nb * 4, TSDF_MEM)) || (rc = d_t.alloc(ctx, bytes, TSDF_MEM)) || (rc = d_w.alloc(ctx, bytes, TSDF_MEM))) return rc;
+    D2R_HIP(ctx, hipMemcpyAsync(d_blocks.get(), blocks.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_tsdf_gather, dim3((uint32_t)nb), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), G, d_blocks.get(), d_t.get(), d_w.get());
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipMemcpyAsync(tsdf, d_t.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(weight, d_w.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return D2R_OK;
 }
 
 int d2r_tsdf_extract(d2r_tsdf *v, float weight_threshold, const float *crop, double cluster_keep, uint32_t *n_vertices, uint32_t *n_triangles,
@@ -812,17 +713,14 @@ int d2r_tsdf_touch_bits(d2r_tsdf *v, float weight_threshold, float contact, uint
     const uint32_t wpr = (G.nv[0] + 31u) / 32u, segs = (G.nv[0] + 63u) / 64u;
     const uint64_t rows = (uint64_t)G.nv[1] * G.nv[2], n_waves = rows * segs;
     const size_t bytes = (size_t)rows * wpr * 4;
-    uint32_t *d_words = nullptr;
-    int rc = tsdf_alloc(ctx, d_words, bytes, false);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_tsdf_touch_bits, dim3((uint32_t)((n_waves + 3) / 4)), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, G, wpr, segs, n_waves,
-                       weight_threshold, contact, d_words);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(words_out, d_words, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = e2;
-    (void)hipFree(d_words);
-    if (e != hipSuccess) return d2r_fail(ctx, D2R_ERR_DEVICE, std::string("d2r_tsdf_touch_bits: ") + hipGetErrorString(e));
+    D2rDev<uint32_t> d_words;
+    D2rDrain drain{ctx->stream};
+    if (int rc = d_words.alloc(ctx, bytes, TSDF_MEM)) return rc;
+    hipLaunchKernelGGL(k_tsdf_touch_bits, dim3((uint32_t)((n_waves + 3) / 4)), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), G, wpr, segs, n_waves,
+                       weight_threshold, contact, d_words.get());
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipMemcpyAsync(words_out, d_words.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return D2R_OK;
 }
 
@@ -834,36 +732,31 @@ int d2r_tsdf_solid_points(d2r_tsdf *v, float weight_threshold, uint32_t *n_point
         return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_solid_points: weight_threshold must be > 0");
     D2R_HIP(ctx, hipSetDevice(v->device));
     const uint32_t nchunks = (uint32_t)(v->n_vox / MC_CHUNK), cap = *n_points;
-    uint32_t *chunk = nullptr;
-    float *d_xyz = nullptr;
-    auto body = [&]() -> int {
-        int r;
-        if ((r = tsdf_alloc(ctx, chunk, (size_t)nchunks * 4, false))) return r;
-        hipLaunchKernelGGL(k_tsdf_solid_count, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, weight_threshold, chunk);
-        hipLaunchKernelGGL(k_tsdf_solid_scan, dim3(1), dim3(TSDF_THREADS), 0, ctx->stream, chunk, nchunks, v->counters);
-        D2R_HIP(ctx, hipGetLastError());
-        uint32_t tot = 0;
-        D2R_HIP(ctx, hipMemcpyAsync(&tot, v->counters + 4, 4, hipMemcpyDeviceToHost, ctx->stream));
-        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        *n_points = tot;
-        if (tot == 0)
-            return d2r_fail(ctx, D2R_ERR_INVALID,
-                            "TSDF volume holds no solid voxel: the object was seen in no frame (no voxel reached the weight threshold with "
-                            "tsdf <= 0)");
-        if (!xyz) return D2R_OK;
-        if (cap < tot) return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_solid_points: buffer smaller than the point set");
-        if ((r = tsdf_alloc(ctx, d_xyz, (size_t)tot * 12, false))) return r;
-        hipLaunchKernelGGL(k_tsdf_solid_emit, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox, chunk, v->G, weight_threshold, d_xyz, tot);
-        D2R_HIP(ctx, hipGetLastError());
-        D2R_HIP(ctx, hipMemcpyAsync(xyz, d_xyz, (size_t)tot * 12, hipMemcpyDeviceToHost, ctx->stream));
-        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return D2R_OK;
-    };
-    const int rc = body();
-    if (rc) (void)hipStreamSynchronize(ctx->stream);
-    for (void *p : {(void *)chunk, (void *)d_xyz})
-        if (p) (void)hipFree(p);
-    return rc;
+    D2rDev<uint32_t> chunk;
+    D2rDev<float> d_xyz;
+    D2rDrain drain{ctx->stream};
+    int r;
+    if ((r = chunk.alloc(ctx, (size_t)nchunks * 4, TSDF_MEM))) return r;
+    hipLaunchKernelGGL(k_tsdf_solid_count, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), weight_threshold, chunk.get());
+    hipLaunchKernelGGL(k_tsdf_solid_scan, dim3(1), dim3(TSDF_THREADS), 0, ctx->stream, chunk.get(), nchunks, v->counters.get());
+    D2R_HIP(ctx, hipGetLastError());
+    uint32_t tot = 0;
+    D2R_HIP(ctx, hipMemcpyAsync(&tot, v->counters.get() + 4, 4, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_points = tot;
+    if (tot == 0)
+        return d2r_fail(ctx, D2R_ERR_INVALID,
+                        "TSDF volume holds no solid voxel: the object was seen in no frame (no voxel reached the weight threshold with "
+                        "tsdf <= 0)");
+    if (!xyz) return D2R_OK;
+    if (cap < tot) return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_solid_points: buffer smaller than the point set");
+    if ((r = d_xyz.alloc(ctx, (size_t)tot * 12, TSDF_MEM))) return r;
+    hipLaunchKernelGGL(k_tsdf_solid_emit, dim3(nchunks), dim3(TSDF_THREADS), 0, ctx->stream, v->vox.get(), chunk.get(), v->G, weight_threshold,
+                       d_xyz.get(), tot);
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipMemcpyAsync(xyz, d_xyz.get(), (size_t)tot * 12, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return D2R_OK;
 }
 
 }  // extern "C"
