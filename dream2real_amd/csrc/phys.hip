@@ -130,6 +130,16 @@ __device__ V3 closest_triangle(V3 *s, int &n)
         s[0] = best_s[0]; s[1] = best_s[1]; n = best_n;
         return best;
     }
+    // interior: the foot of the perpendicular, n (a . n) / (n . n).  The barycentric form a + v ab + w ac carries a rounding
+    // error of eps |a| in every component, sideways ones included; against a static shape metres wide (a table) and a gap of
+    // millimetres that turns v by 1e-4 rad, the support point along -v is then a vertex already held, and the lower bound
+    // v . w / |v| is off by 1e-4 m (round 14: 1000 extreme vertices 2 mm over a 2 m slab answered "apart" at 1.97 mm)
+    const V3 nrm = cross(ab, ac);
+    const float nn = dot(nrm, nrm);
+    if (nn > 0.f && nn < INFINITY) {
+        const float t = dot(a, nrm) / nn;
+        return {t * nrm.x, t * nrm.y, t * nrm.z};
+    }
     const float den = 1.f / sum, v = vb * den, w = vc * den;
     return {fmaf(w, ac.x, fmaf(v, ab.x, a.x)), fmaf(w, ac.y, fmaf(v, ab.y, a.y)), fmaf(w, ac.z, fmaf(v, ab.z, a.z))};
 }

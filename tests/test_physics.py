@@ -160,24 +160,7 @@ def test_oracle_flow_on_a_table_scene():
     assert not phys_ref.unsupcol_check(poses, init, movable, statics, res, v0, table_z=-0.3)[0]
 
 
-BAND = 5e-6      # metres of collision margin = 1e-5 m of hull distance
-
-
-def assert_equal_away_from_band(got, want_fn, margin, what=""):
-    """The GPU decides contact by float32 distance GJK, the oracle by an LP / QP in double: a pair whose hull distance lies
-    within BAND-rounding of the contact distance 2 * margin may fall either way; everywhere else the masks must be EQUAL.
-    Checked as: every pose's GPU answer equals the oracle's answer for the margin itself or for a margin BAND smaller or
-    larger (a contact distance within +-1e-5 m)."""
-    w0 = want_fn(margin)
-    ok = got == w0
-    n_off = int((~ok).sum())
-    if n_off:
-        ok |= got == want_fn(max(0.0, margin - BAND))
-        ok |= got == want_fn(margin + BAND)
-    print(f"[parity] physics {what} margin {margin}: {n_off} of {len(got)} poses differ from the oracle at the margin itself, "
-          f"{int((~ok).sum())} outside the +-{2 * BAND:.0e} m band")
-    assert ok.all(), (what, margin, np.nonzero(~ok)[0][:10])
-    return w0
+from tests.phys_cases import BAND, assert_equal_away_from_band  # noqa: E402,F401
 
 
 @pytest.mark.gpu
