@@ -27,6 +27,7 @@ EXPORTS = [
     "d2r_sdfphys_create", "d2r_sdfphys_destroy", "d2r_sdfphys_check", "d2r_sdfphys_get_timing",
     "d2r_png_write_channels", "d2r_png_info", "d2r_png_read_grey", "d2r_png_read_rgb",
     "d2r_scene_bound_masks", "d2r_masks_prune", "d2r_masks_components", "d2r_masks_lut", "d2r_masks_get_timing",
+    "d2r_pcd_build", "d2r_pcd_size", "d2r_pcd_read", "d2r_pcd_build_get_timing",
 ]
 
 
@@ -342,6 +343,45 @@ def masks_timing(ctx):
     """d2r_masks_get_timing -> (upload, kernels, download) of the context's last batch mask call, device-event milliseconds."""
     ms = np.zeros(3, np.float64)
     check(load().d2r_masks_get_timing(_h(ctx), ptr(ms)), _h(ctx))
+    return tuple(float(x) for x in ms)
+
+
+def pcd_build(ctx, rgb, depth_u16, labels, cam_poses, K, bounds, voxel: float, views, obj_ids):
+    """d2r_pcd_build: uint8 rgb [n,h,w,3], uint16 millimetre depth [n,h,w], uint8 labels [n,h,w], fp64 poses [n,4,4], K [3,3], bounds
+    [[min xyz],[max xyz]], voxel (0: no down-sampling), frame indices `views`, labels `obj_ids` -> one d2r_pcd handle per object id
+    (DESIGN.md section 2b); each goes to d2r_pcd_render as it is, to pcd_read for its points, and to d2r_pcd_destroy in the end."""
+    c = np.ascontiguousarray(rgb, np.uint8)
+    d = _frames(depth_u16, np.uint16, "depth_u16")
+    m = _frames(labels, np.uint8, "labels")
+    n, h, w = d.shape
+    if c.shape != (n, h, w, 3) or m.shape != d.shape:
+        raise ValueError(f"rgb {c.shape}, depth {d.shape} and labels {m.shape} do not describe the same frames")
+    T = np.ascontiguousarray(cam_poses, np.float64).reshape(-1, 16)
+    if T.shape[0] != n:
+        raise ValueError(f"{T.shape[0]} poses for {n} frames")
+    Kd = np.ascontiguousarray(K, np.float64).reshape(9)
+    b = np.ascontiguousarray(bounds, np.float64).reshape(6)
+    vw = np.ascontiguousarray(views, np.uint32).reshape(-1)
+    ids = np.ascontiguousarray(obj_ids, np.uint8).reshape(-1)
+    out = (C.c_void_p * max(1, ids.size))()
+    check(load().d2r_pcd_build(_h(ctx), ptr(c), ptr(d), ptr(m), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(T), ptr(Kd), ptr(b),
+                               C.c_double(voxel), ptr(vw), C.c_uint32(vw.size), ptr(ids), C.c_uint32(ids.size), out), _h(ctx))
+    return [C.c_void_p(out[i]) for i in range(ids.size)]
+
+
+def pcd_read(ctx, handle):
+    """d2r_pcd_size + d2r_pcd_read: a device cloud -> (xyz float32 [n,3], rgb uint8 [n,3])."""
+    n = C.c_uint32()
+    check(load().d2r_pcd_size(handle, C.byref(n)))
+    xyz, rgb = np.empty((n.value, 3), np.float32), np.empty((n.value, 3), np.uint8)
+    check(load().d2r_pcd_read(_h(ctx), handle, ptr(xyz), ptr(rgb)), _h(ctx))
+    return xyz, rgb
+
+
+def pcd_build_timing(ctx):
+    """d2r_pcd_build_get_timing -> (upload, kernels) of the context's last d2r_pcd_build, device-event milliseconds."""
+    ms = np.zeros(2, np.float64)
+    check(load().d2r_pcd_build_get_timing(_h(ctx), ptr(ms)), _h(ctx))
     return tuple(float(x) for x in ms)
 
 

@@ -327,6 +327,8 @@ void d2r_ctx_destroy(d2r_ctx *c)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->mask_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->pcdb_ev)
+        if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; k++)
         if (c->frame_host[k]) (void)hipHostFree(c->frame_host[k]);
     if (c->render_stream) (void)hipStreamDestroy(c->render_stream);

@@ -131,6 +131,8 @@ struct d2r_ctx {
     Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots, result frames, union-find parents + component statistics of a pass
     hipEvent_t mask_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... upload / kernels / download boundaries of the last batch call (d2r_masks_get_timing)
     bool mask_timed = false;
+    hipEvent_t pcdb_ev[3] = {nullptr, nullptr, nullptr};   // pcdbuild.hip: upload / kernels boundaries of the last d2r_pcd_build (d2r_pcd_build_get_timing)
+    bool pcdb_timed = false;
     Buf lens_tab;                // undistorted camera-space directions of the current view's pixels (nerf.hip lens_table)
     float lens_key[10] = {};     // ... and the view (size, intrinsics, coefficients) it was computed for
     bool lens_key_valid = false;
@@ -214,6 +216,14 @@ struct d2r_nerf {
     D2rDev<uint32_t> d_grid, d_brick_tab, d_gbrick_tab;
     D2rDev<uint64_t> d_bricks;
     D2rDev<uint4> d_wfrag;
+};
+
+// a coloured point cloud on a device: uploaded by d2r_pcd_create (pcd.hip) or built there by d2r_pcd_build (pcdbuild.hip)
+struct d2r_pcd {
+    int device = 0;
+    uint32_t n = 0;
+    D2rDev<float4> xyz;          // [n] (x, y, z, 0)
+    D2rDev<uint32_t> rgb;        // [n] r | g << 8 | b << 16
 };
 
 // hipFuncSetAttribute once per (kernel instantiation, device), safe when different contexts are driven from

@@ -18,13 +18,6 @@
 
 #include "d2r_internal.h"
 
-struct d2r_pcd {
-    int device = 0;
-    uint32_t n = 0;
-    D2rDev<float4> xyz;          // [n] (x, y, z, 0)
-    D2rDev<uint32_t> rgb;        // [n] r | g << 8 | b << 16
-};
-
 namespace {
 
 constexpr uint32_t PCD_THREADS = 256;

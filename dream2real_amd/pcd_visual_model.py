@@ -308,16 +308,44 @@ def voxel_down_sample(xyz, rgb, voxel: float):
     return mean, np.floor(col + 0.5).astype(np.uint8)
 
 
+def _get_vis_pcds_device(ctx, rgbs, depths, cam_poses, intrinsics, masks, num_objs, scene_bounds, views, voxel):
+    """The clouds of get_vis_pcds from one d2r_pcd_build call (pcdbuild.hip): the frames stacked once, every object at once."""
+    labels = np.stack([_np(m) for m in masks])
+    if labels.size and (labels.min() < 0 or labels.max() > 255):
+        raise ValueError(f"the device path takes labels 0 .. 255, the masks hold {int(labels.min())} .. {int(labels.max())}")
+    if num_objs > 256:
+        raise ValueError(f"the device path takes object ids 0 .. 255, num_objs is {num_objs}")
+    d16 = np.stack([(_np(d).astype(np.float32) * 1000).astype(np.uint16) for d in depths])
+    rgb = np.stack([_np(c).astype(np.uint8) for c in rgbs])
+    poses = np.stack([np.asarray(_np(T), np.float64) for T in cam_poses])
+    handles = _lib.pcd_build(ctx, rgb, d16, labels.astype(np.uint8), poses, intrinsics, scene_bounds, voxel, list(views),
+                             list(range(num_objs)))
+    try:
+        return [PointCloud(*_lib.pcd_read(ctx, h)) for h in handles]
+    finally:
+        for h in handles:
+            _lib.load().d2r_pcd_destroy(h)
+
+
 def get_vis_pcds(rgbs, depths, cam_poses, intrinsics, masks, num_objs, scene_bounds, save_dir=None, vis=False,
-                 use_cache=True, pcds_type=1, single_view_idx=0):
+                 use_cache=True, pcds_type=1, single_view_idx=0, *, ctx=None):
     """reference vision_3d/pcd_visual_model.py:18-95: one PointCloud per object id (0 .. num_objs - 1) from the masked
     RGB-D frames, or read from <save_dir>/obj_vis_{id}.pcd with use_cache.  pcds_type 0: the view single_view_idx alone;
-    1: every view, each voxel-downsampled at 0.002 before they are concatenated.  `vis` (an Open3D window) is ignored."""
+    1: every view, each voxel-downsampled at 0.002 before they are concatenated.  `vis` (an Open3D window) is ignored.
+    With `ctx` (an engine.Context or a d2r_ctx pointer) the clouds are built on the GPU by one d2r_pcd_build call, bit for bit
+    the ones the host path below gives; without it they are built here in numpy."""
     if use_cache:
         return [read_point_cloud(os.path.join(save_dir, f"obj_vis_{obj_id}.pcd")) for obj_id in range(num_objs)]
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
     views = range(len(depths)) if pcds_type == 1 else [single_view_idx]
+    if ctx is not None:
+        out = _get_vis_pcds_device(ctx, rgbs, depths, cam_poses, intrinsics, masks, num_objs, scene_bounds, views,
+                                   FRAME_VOXEL_SIZE if pcds_type == 1 else 0.0)
+        if save_dir is not None:
+            for obj_id, pcd in enumerate(out):
+                write_point_cloud(os.path.join(save_dir, f"obj_vis_{obj_id}.pcd"), pcd)
+        return out
     out = []
     for obj_id in range(num_objs):
         parts_xyz, parts_rgb = [], []

@@ -70,7 +70,7 @@ class TaskModel:
             from .pcd_visual_model import get_vis_pcds
             vis_model = get_vis_pcds(scene_model.rgbs, scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, task_bground_masks, 1,
                                      scene_model.scene_bounds, save_dir=save_dir, vis=False, use_cache=use_cache, pcds_type=pcds_type,
-                                     single_view_idx=single_view_idx)[0]
+                                     single_view_idx=single_view_idx, ctx=ctx)[0]
         else:
             from .ngp_visual_model import get_vis_ngps
             vis_model = get_vis_ngps(scene_model.rgbs, task_bground_masks, scene_model.scene_type, use_cache=use_cache, data_dir=data_dir, fg=False,
@@ -93,7 +93,7 @@ class TaskModel:
             from .pcd_visual_model import get_vis_pcds
             return get_vis_pcds(scene_model.rgbs, scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, movable_masks, 1,
                                 scene_model.scene_bounds, save_dir=save_dir, vis=False, use_cache=use_cache, pcds_type=pcds_type,
-                                single_view_idx=single_view_idx)[0]
+                                single_view_idx=single_view_idx, ctx=ctx)[0]
         from .ngp_visual_model import get_vis_ngps
         return get_vis_ngps(scene_model.rgbs, movable_masks, scene_model.scene_type, use_cache=use_cache, data_dir=data_dir, fg=True, ctx=ctx)
 

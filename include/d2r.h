@@ -641,6 +641,37 @@ D2R_API int d2r_pcd_render_score_host(d2r_ctx *ctx, const d2r_pcd *bg, const d2r
                                       const float *obj_poses, uint32_t K, const float *text_embeds, uint32_t C,
                                       float logit_scale, float *logits_out, uint8_t *frames_out);
 
+/*
+ * The ablation's visual clouds built on the device (reference vision_3d/pcd_visual_model.py:18-95, get_vis_pcds; the rule is
+ * DESIGN.md section 2b, bullet "Clouds"): one call, every listed view, every listed object.
+ *   rgb         host [n][h][w][3] uint8
+ *   depth_u16   host [n][h][w] millimetres ((depth * 1000).astype(uint16) of the metric depth)
+ *   labels      host [n][h][w] uint8 label image
+ *   cam_poses   host [n][16] fp64 row-major camera-to-world poses, used as given (not inverted)
+ *   K           host [9] fp64 intrinsics; bounds host [2][3] fp64 crop box, inclusive on both ends
+ *   voxel       0: every surviving point in pixel order (pcds_type 0); > 0: each (object, view) segment voxel-downsampled
+ *   views       host [n_views] frame indices, each < n; an object's cloud is its views' segments in this order
+ *   obj_ids     host [n_objs] labels, each listed once
+ *   out         host [n_objs] receives one handle per object (d2r_pcd_destroy each); d2r_pcd_render takes them as they are
+ * A pixel with label L belongs to object L iff every in-frame pixel of the 15 x 15 window centred on it carries L and its depth
+ * is not 0; z = (double)((float)d16 / 1000.0f), x = ((j - cx) z) / fx, y = ((i - cy) z) / fy, world_r = ((T[r][0] x + T[r][1] y) +
+ * T[r][2] z) + T[r][3] in fp64; points outside the bounds are dropped.  With voxels, per segment: origin = min - voxel / 2, index =
+ * floor((p - origin) / voxel), voxels in ascending (ix, iy, iz), each the fp64 sum of its points in pixel order divided by their
+ * count and rounded to fp32, each colour channel floor(sum / count + 0.5).
+ * Refused with D2R_ERR_INVALID before any device work: null or zero-size arguments, a view index >= n, an object id listed twice,
+ * non-finite poses or intrinsics, a negative voxel, and bounds for which (max - min) / voxel + 2 needs more than 21 bits on an axis.
+ * On any failure every out[] entry is NULL and nothing is left allocated.  Synchronous.
+ */
+D2R_API int d2r_pcd_build(d2r_ctx *ctx, const uint8_t *rgb, const uint16_t *depth_u16, const uint8_t *labels, uint32_t n, uint32_t w,
+                          uint32_t h, const double *cam_poses, const double *K, const double *bounds, double voxel,
+                          const uint32_t *views, uint32_t n_views, const uint8_t *obj_ids, uint32_t n_objs, d2r_pcd **out);
+/* The number of points of a cloud; its points to the host: xyz [n][3] fp32, rgb [n][3] uint8 (both may be NULL when n is 0). */
+D2R_API int d2r_pcd_size(const d2r_pcd *pcd, uint32_t *n);
+D2R_API int d2r_pcd_read(d2r_ctx *ctx, const d2r_pcd *pcd, float *xyz, uint8_t *rgb);
+/* Device-event times of the last d2r_pcd_build on this context: ms_out host [2] = upload, kernels (the three small count reads that
+ * size the buffers included), milliseconds. */
+D2R_API int d2r_pcd_build_get_timing(d2r_ctx *ctx, double *ms_out);
+
 /* ------------------------------------------------- TSDF fusion of RGB-D frames into a triangle mesh (use_phys_tsdf)
  *
  * replaces the TSDF branch of reference vision_3d/physics_utils.py:58-115 (get_phys_models: Open3D VoxelBlockGrid on the
