@@ -28,6 +28,7 @@ EXPORTS = [
     "d2r_png_write_channels", "d2r_png_info", "d2r_png_read_grey", "d2r_png_read_rgb",
     "d2r_scene_bound_masks", "d2r_masks_prune", "d2r_masks_components", "d2r_masks_lut", "d2r_masks_get_timing",
     "d2r_pcd_build", "d2r_pcd_size", "d2r_pcd_read", "d2r_pcd_build_get_timing",
+    "d2r_masks_census",
 ]
 
 
@@ -337,6 +338,15 @@ def masks_lut(ctx, masks, lut, oob=None, alpha: bool = False):
     check(load().d2r_masks_lut(_h(ctx), ptr(m), ptr(o), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(t), ptr(out), ptr(al)),
           _h(ctx))
     return (out, al) if alpha else out
+
+
+def masks_census(ctx, masks):
+    """d2r_masks_census: uint8 labels [n,h,w] -> uint32 [n,256], the pixels of every label in every frame."""
+    m = _frames(masks, np.uint8, "masks")
+    n, h, w = m.shape
+    out = np.empty((n, 256), np.uint32)
+    check(load().d2r_masks_census(_h(ctx), ptr(m), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(out)), _h(ctx))
+    return out
 
 
 def masks_timing(ctx):

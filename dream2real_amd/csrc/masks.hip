@@ -12,6 +12,8 @@
 //   k_select_*       per label: component count, best distance (bit pattern of a non-negative double) or area, tie rule
 //   k_prune_write    the pruned label image with the out-of-scene overwrite
 //   k_mask_lut       out = lut[mask] | (oob != 0), optionally alpha = 255 (1 - out)
+//   k_census         pixels per label per frame: one 256-bin LDS histogram per wave, 16 pixels per load, equal neighbours of a lane
+//                    merged into one LDS add, the workgroup's bins flushed with integer atomics to the frame's row
 // Every value is written by ordinary vector stores from C++.
 #include <math.h>
 #include <stdlib.h>
@@ -28,6 +30,7 @@ constexpr uint32_t MK_THREADS = 256;
 constexpr int CL_TW = 4, CL_TR = 64, CL_ROWS = 128;      // k_morph: words x output rows of a tile, rows held (CL_TR + 63 <= CL_ROWS)
 constexpr int LB_TW = 64, LB_TH = 16, LB_PX = LB_TW * LB_TH;   // k_label_tiles: tile of the per-tile labelling
 constexpr uint32_t NO_KEY = 0xffffffffu;
+constexpr uint32_t CS_ITERS = 8, CS_SEGS = MK_THREADS * CS_ITERS;   // k_census: 16-byte segments per lane, per workgroup (32 KiB of pixels)
 constexpr size_t MK_WS_BUDGET = (size_t)1 << 30;         // labelling workspace per pass of frames (D2R_MASKS_WS_BYTES overrides it)
 
 struct MaskCam {
@@ -419,6 +422,49 @@ __global__ __launch_bounds__(MK_THREADS) void k_mask_lut(const uint8_t *__restri
     }
 }
 
+// counts[f][l] += pixels of frame f with label l.  The batch is one byte range that starts 256-byte aligned; frame f is its bytes
+// [f px, (f + 1) px), which begin and end anywhere.  The range is cut into the batch's aligned 16-byte segments: a segment inside
+// the frame is one uint4 load, the (at most two) segments that straddle a frame's end are read byte by byte inside the frame only.
+__global__ __launch_bounds__(MK_THREADS) void k_census(const uint8_t *__restrict__ mask, size_t px, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t hist[MK_THREADS / 64][256];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t e = 0; e < MK_THREADS / 64; ++e) hist[e][t] = 0;
+    __syncthreads();
+    uint32_t *h = hist[t >> 6];
+    const size_t lo = (size_t)blockIdx.y * px, hi = lo + px;
+    const size_t seg1 = (hi + 15) / 16, first = lo / 16 + (size_t)blockIdx.x * CS_SEGS + t;
+    for (uint32_t it = 0; it < CS_ITERS; ++it) {
+        const size_t s = first + (size_t)it * MK_THREADS;
+        if (s >= seg1) break;
+        const size_t b = s * 16;
+        if (b >= lo && b + 16 <= hi) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(mask + b);
+            const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+            uint32_t cur = wd[0] & 0xffu, run = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint32_t l = (wd[k >> 2] >> (8 * (k & 3))) & 0xffu;
+                if (l == cur) {
+                    ++run;
+                } else {
+                    atomicAdd(&h[cur], run);
+                    cur = l;
+                    run = 1;
+                }
+            }
+            atomicAdd(&h[cur], run);
+        } else {
+            const size_t a = b < lo ? lo : b, z = b + 16 < hi ? b + 16 : hi;
+            for (size_t e = a; e < z; ++e) atomicAdd(&h[mask[e]], 1u);
+        }
+    }
+    __syncthreads();
+    uint32_t sum = 0;
+    for (uint32_t e = 0; e < MK_THREADS / 64; ++e) sum += hist[e][t];
+    if (sum) atomicAdd(&counts[(size_t)blockIdx.y * 256 + t], sum);
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 int masks_check_frames(d2r_ctx *ctx, uint32_t n, uint32_t w, uint32_t h)
@@ -642,6 +688,32 @@ int d2r_masks_lut(d2r_ctx *ctx, const uint8_t *masks_u8, const uint8_t *oob_u8, 
     D2R_HIP(ctx, hipMemcpyAsync(out_u8, ob, tot, hipMemcpyDeviceToHost, ctx->stream));
     if (alpha_out_u8) D2R_HIP(ctx, hipMemcpyAsync(alpha_out_u8, ob + seg, tot, hipMemcpyDeviceToHost, ctx->stream));
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return D2R_OK;
+}
+
+int d2r_masks_census(d2r_ctx *ctx, const uint8_t *masks_u8, uint32_t n, uint32_t w, uint32_t h, uint32_t *counts_out)
+{
+    if (!ctx) return d2r_fail(ctx, D2R_ERR_INVALID, "null context");
+    if (!masks_u8 || !counts_out) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = masks_check_frames(ctx, n, w, h))) return rc;
+    D2R_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = masks_events(ctx))) return rc;
+    const size_t px = (size_t)w * h, tot = px * n, out_bytes = (size_t)n * 256 * sizeof(uint32_t);
+    if ((rc = d2r_reserve(ctx, ctx->mask_in, tot)) || (rc = d2r_reserve(ctx, ctx->mask_out, out_bytes))) return rc;
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[0], ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(ctx->mask_in.p, masks_u8, tot, hipMemcpyHostToDevice, ctx->stream));
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[1], ctx->stream));
+    D2R_HIP(ctx, hipMemsetAsync(ctx->mask_out.p, 0, out_bytes, ctx->stream));
+    const size_t segs = px / 16 + 2;                         // a frame overlaps at most this many aligned segments of the batch
+    hipLaunchKernelGGL(k_census, dim3((uint32_t)((segs + CS_SEGS - 1) / CS_SEGS), n), dim3(MK_THREADS), 0, ctx->stream,
+                       (const uint8_t *)ctx->mask_in.p, px, (uint32_t *)ctx->mask_out.p);
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[2], ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(counts_out, ctx->mask_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[3], ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->mask_timed = true;
     return D2R_OK;
 }
 

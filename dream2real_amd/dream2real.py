@@ -1,17 +1,21 @@
-"""The caller of the render-and-score path: `ImaginationEngine.dream_best_pose` (reference dream2real.py:286-358) on
-the MI355X library — physics pre-filter, renderer, `optimise_pose_grid`, and the three text files the reference
-persists, in the reference's order and with its switches.
+"""The reference's `ImaginationEngine` (dream2real.py:43-358) on the MI355X library, all three calls a user makes:
+`build_scene_model` (frames, scene-bound masks, label masks, the label census, camera poses, physics models, captions),
+`interpret_user_instr` (movable and relevant objects, lazy physics models, the two visual models, the task masks) and
+`dream_best_pose` (physics pre-filter, renderer, `optimise_pose_grid`, the three text files), in the reference's order and
+with its switches.  `PathConfig.from_json` reads the reference's settings files.
 
-Only the part of the reference's engine that drives the path is mirrored: what comes before it (segmentation, captioning,
-LLM parsing, NeRF training, mesh extraction — `build_scene_model`, `build_task_model`) and what comes after it (cost-volume
-visualisation, robot execution) is outside the path.  The engine object the reference keeps
-these settings on (`cfg.*`, dream2real.py:40-99) is a plain settings class here; `ctx` (an engine.Context) stands where the
-reference talks to PyBullet and pyngp, and `scorer` (+ text embeddings or a text encoder and tokenizer) where it
-downloads CLIP.
+The models the reference downloads enter from outside: segmentation (SAM, XMem) as a `segmentor(rgbs, depths)` callable or
+the XMem_masks cache, captioning as a `captions` list or the captions.json cache, the LLM as a `lang_model` object (any
+object with `parse_instr`, `get_movable_obj_idx`, `get_relevant_obj_idxs`; `CachedLangModel` answers from a JSON file), CLIP
+as `scorer` (+ text embeddings, or a text encoder and tokenizer).  NeRF training still raises: camera poses come from
+opt_cam_poses.npy or, with `use_vis_pcds`, from poses.txt, and NeRF visual models from their snapshot cache.  What comes
+after the path (cost-volume visualisation, robot execution) stays outside it.  `ctx` (an
+engine.Context) stands where the reference talks to PyBullet, Open3D and pyngp.
 """
 from __future__ import annotations
 
 import dataclasses
+import json
 import os
 from typing import Optional, Sequence
 
@@ -22,7 +26,7 @@ from . import clip_scoring, combined_rendering, physics_utils
 
 @dataclasses.dataclass
 class PathConfig:
-    """The `cfg` fields dream_best_pose reads (reference dream2real.py:40-99, cfg.py)."""
+    """The `cfg` fields the engine reads (reference dream2real.py:40-99, cfg.py)."""
     data_dir: str
     sample_res: Sequence[int]
     scene_type: int = 0
@@ -37,6 +41,106 @@ class PathConfig:
     use_vis_pcds: bool = False
     resolution: Optional[Sequence[int]] = None         # renderer resolution (w, h); None = the reference's 336 x 336
     save_renders: bool = True                          # cb_render/cb_rgb_%04d.png per valid pose (the reference always does: clip_scoring.py:140)
+    # what build_scene_model and interpret_user_instr read (cfg.py:19-53, 75-81)
+    render_distractors: bool = False
+    pcds_type: Optional[int] = None                    # 0: the view single_view_idx alone, 1: every view; None without use_vis_pcds
+    single_view_idx: int = 0
+    use_cache_dynamic_masks: bool = False
+    use_cache_segs: bool = False
+    use_cache_cam_poses: bool = False
+    use_cache_captions: bool = False
+    use_cache_phys: bool = False
+    use_cache_vis: bool = False
+    use_cache_llm: bool = False
+    use_phys_tsdf: bool = True
+    multi_view_captions: bool = False
+    scene_centre: Optional[Sequence[float]] = None
+    scene_phys_bounds: Optional[Sequence[Sequence[float]]] = None      # [[xmin, ymin, zmin], [xmax, ymax, zmax]]
+    width: int = 1280
+    height: int = 720
+    phys_backend: str = "hulls"                        # physics_utils.PHYS_BACKENDS; not a key of the reference's files
+
+    # engine keys read as they are; pcds_type, single_view_idx and phys_backend have their own rules below
+    _ENGINE_KEYS = ("sample_res", "scene_type", "render_cam_pose_idx", "use_phys", "lazy_phys_mods", "use_cache_renders",
+                    "use_cache_goal_pose", "spatial_smoothing", "physics_only", "use_vis_pcds", "render_distractors",
+                    "use_cache_dynamic_masks", "use_cache_segs", "use_cache_cam_poses", "use_cache_captions", "use_cache_phys",
+                    "use_cache_vis", "use_cache_llm", "use_phys_tsdf", "multi_view_captions", "scene_centre", "scene_phys_bounds")
+
+    @classmethod
+    def from_json(cls, config_file, data_dir, **overrides):
+        """The reference's settings format (configs/*/*.json) as cfg.py:19-53, 75-81 reads it: the `engine` group and the
+        frame size of the `camera` group; `trainer`, `vis`, `robot` and the rest are not read.  `single_view_idx` defaults
+        to 0, `pcds_type` is read only with `use_vis_pcds`, `engine.phys_backend` is this package's own optional key.  A key
+        the path needs and the file lacks is a KeyError naming group.key.  `overrides` set the fields no file carries
+        (embodied, resolution, save_renders) or replace what was read."""
+        with open(config_file) as f:
+            config = json.load(f)
+
+        def need(group, key):
+            if group not in config or key not in config[group]:
+                raise KeyError(f"{group}.{key}")
+            return config[group][key]
+
+        fields = {key: need("engine", key) for key in cls._ENGINE_KEYS}
+        fields["pcds_type"] = need("engine", "pcds_type") if fields["use_vis_pcds"] else None
+        fields["single_view_idx"] = config["engine"].get("single_view_idx", 0)
+        fields["phys_backend"] = config["engine"].get("phys_backend", "hulls")
+        fields["width"], fields["height"] = need("camera", "w"), need("camera", "h")
+        fields.update(overrides)
+        return cls(data_dir=data_dir, **fields)
+
+
+class CachedLangModel:
+    """A language model that answers from a JSON file of {method: {key: answer}}: the three calls interpret_user_instr
+    makes, each keyed by the JSON text of its argument list (`key`).  `record` adds an answer, `save` writes the file; a
+    question the file does not hold is a KeyError naming the method and the key."""
+
+    METHODS = ("parse_instr", "get_movable_obj_idx", "get_relevant_obj_idxs")
+
+    def __init__(self, path):
+        self.path = path
+        self.answers = {m: {} for m in self.METHODS}
+        if os.path.exists(path):
+            with open(path) as f:
+                for method, table in json.load(f).items():
+                    if method not in self.METHODS:
+                        raise ValueError(f"{path}: unknown method {method!r} (expected one of {self.METHODS})")
+                    self.answers[method].update(table)
+
+    @staticmethod
+    def key(*args) -> str:
+        return json.dumps(list(args), ensure_ascii=False, separators=(",", ":"))
+
+    def record(self, method, args, answer):
+        if method not in self.METHODS:
+            raise ValueError(f"unknown method {method!r} (expected one of {self.METHODS})")
+        self.answers[method][self.key(*args)] = answer
+        return self
+
+    def save(self):
+        with open(self.path, "w") as f:
+            json.dump(self.answers, f, indent=1, ensure_ascii=False)
+
+    def _answer(self, method, *args):
+        k = self.key(*args)
+        if k not in self.answers[method]:
+            raise KeyError(f"{self.path}: no cached answer for {method}{k}")
+        return self.answers[method][k]
+
+    def parse_instr(self, user_instr):
+        """-> (goal_caption, norm_caption)"""
+        goal_caption, norm_caption = self._answer("parse_instr", user_instr)
+        return goal_caption, norm_caption
+
+    def get_movable_obj_idx(self, user_instr, obj_captions):
+        return int(self._answer("get_movable_obj_idx", user_instr, list(obj_captions)))
+
+    def get_relevant_obj_idxs(self, norm_caption, obj_captions, movable_obj_idx):
+        return [int(i) for i in self._answer("get_relevant_obj_idxs", norm_caption, list(obj_captions), int(movable_obj_idx))]
+
+
+def _np(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
 def compose_checks(checks):
@@ -50,16 +154,154 @@ def compose_checks(checks):
 
 
 class ImaginationEngine:
-    """The slice of the reference's ImaginationEngine around dream_best_pose."""
+    """The reference's ImaginationEngine: build_scene_model, interpret_user_instr, dream_best_pose."""
 
-    def __init__(self, cfg: PathConfig, ctx, scorer, *, text_embeds=None, text_encoder=None, tokenizer=None, depths_gt=None):
+    def __init__(self, cfg: PathConfig, ctx, scorer, *, text_embeds=None, text_encoder=None, tokenizer=None, depths_gt=None,
+                 lang_model=None, segmentor=None, intrinsics=None):
         self.cfg, self.ctx, self.scorer = cfg, ctx, scorer
         self.text_embeds, self.text_encoder, self.tokenizer = text_embeds, text_encoder, tokenizer
         self.depths_gt = depths_gt                       # [L, h, w] sensor depth of the render views (dream2real.py:117-118), or None
         self.data_dir = cfg.data_dir
+        self.lang_model, self.segmentor = lang_model, segmentor
+        if intrinsics is None:
+            from .scene import INTRINSICS_REALSENSE_1280
+            intrinsics = INTRINSICS_REALSENSE_1280
+        self.intrinsics = np.asarray(intrinsics, np.float64)
+        self.topdown = cfg.scene_type in (0, 3)                                                  # :69
+        self.scene_model = None
+        self.out_scene_bound_masks = None
         self.static_phys_handles = None
         self.movable_phys_handle = None
         self.renderer = None
+
+    def build_scene_model(self, raw_data=None, *, captions=None):
+        """reference dream2real.py:101-177.  raw_data: (rgbs uint8 [N,H,W,3], depths [N,H,W] metres, T_WC [N,4,4]), default the
+        frames of data_dir.  captions: one name per object, "__background__" first; default the captions.json of data_dir.
+        Sets self.scene_model, self.out_scene_bound_masks and self.depths_gt."""
+        import torch
+        from . import segmentation
+        from .data_loader import d2r_dataloader
+        from .scene_model import ObjectModel, SceneModel
+        cfg = self.cfg
+        if cfg.scene_centre is None or cfg.scene_phys_bounds is None or cfg.sample_res is None:                    # :94-96
+            raise ValueError("build_scene_model needs cfg.scene_centre, cfg.scene_phys_bounds and cfg.sample_res")
+        intrinsics = self.intrinsics
+        loader = d2r_dataloader(cfg, self.ctx)
+        if raw_data is None:
+            rgbs, depths, raw_cam_poses = loader.load_rgbds()
+        else:
+            rgbs, depths, raw_cam_poses = (_np(a) for a in raw_data)
+            loader.rgb_data, loader.depth_data, loader.T_WC_data = rgbs, depths, np.asarray(raw_cam_poses, np.float32).reshape(-1, 4, 4)
+            loader.size = len(depths)
+        self.out_scene_bound_masks = loader.remove_background(intrinsics, cfg.scene_phys_bounds, use_cache=cfg.use_cache_dynamic_masks)
+
+        self.depths_gt = np.stack([_np(depths[i]) for i in cfg.render_cam_pose_idx])                              # :117-118
+
+        if cfg.use_cache_segs:                                                                                    # :121-137
+            masks = segmentation.load_cached_masks(self.data_dir, len(depths))
+        elif self.segmentor is not None:
+            raw_masks = np.asarray(_np(self.segmentor(rgbs, depths)), np.uint8)
+            masks = segmentation.refine_masks(raw_masks, depths, loader.T_WC_data, intrinsics, self.out_scene_bound_masks,
+                                              cfg.scene_centre, self.data_dir, ctx=self.ctx)
+        else:
+            raise RuntimeError("build_scene_model: running SAM and XMem is out of scope; either set use_cache_segs and provide "
+                               "XMem_masks/rgb_%04d.png in data_dir, or pass segmentor=callable(rgbs, depths) -> uint8 [N,H,W] "
+                               "raw label images to the engine")
+
+        _, num_objs, self.label_counts = segmentation.label_census(masks, ctx=self.ctx)                           # :139-144
+        if num_objs == 0:
+            raise ValueError("build_scene_model: the masks hold no label below 255: every pixel is outside the scene bounds")
+
+        if cfg.use_cache_cam_poses:                                                                               # :146-151
+            opt_cam_poses = np.load(os.path.join(self.data_dir, "opt_cam_poses.npy"))
+        elif cfg.use_vis_pcds:
+            opt_cam_poses = np.asarray(loader.T_WC_data)           # the ablation renders clouds: no NeRF, no pose optimisation
+            np.save(os.path.join(self.data_dir, "opt_cam_poses.npy"), opt_cam_poses)
+        else:
+            raise NotImplementedError("build_scene_model: optimised camera poses come out of NeRF training, which is not implemented; "
+                                      "set use_cache_cam_poses (opt_cam_poses.npy in data_dir) or use_vis_pcds")
+        opt_cam_poses = [torch.tensor(pose) for pose in opt_cam_poses]
+
+        if cfg.lazy_phys_mods:                                                                                    # :153-160
+            phys_models, init_poses = [None] * num_objs, [None] * num_objs
+        else:
+            phys_models, init_poses = physics_utils.get_phys_models(
+                depths, opt_cam_poses, intrinsics, masks, num_objs, cfg.scene_phys_bounds, save_dir=os.path.join(self.data_dir, "phys_mods/"),
+                vis=not cfg.use_cache_phys, use_cache=cfg.use_cache_phys, use_phys_tsdf=cfg.use_phys_tsdf, ctx=self.ctx,
+                phys_backend=cfg.phys_backend)
+
+        captions_path = os.path.join(self.data_dir, "captions.json")                                              # :83, :162-164
+        given = captions is not None
+        if not given:
+            if not os.path.exists(captions_path):
+                raise RuntimeError(f"build_scene_model: captioning models are out of scope; pass captions=[...] or provide {captions_path}")
+            with open(captions_path) as f:
+                captions = json.load(f)
+        captions = list(captions)
+        if len(captions) != num_objs or captions[0] != "__background__":
+            raise ValueError(f"build_scene_model: {len(captions)} captions {captions} for {num_objs} objects (labels 0 .. {num_objs - 1}); "
+                             'there must be one per object and the first must be "__background__"')
+        if given and not cfg.use_cache_captions:                   # the reference's captioner leaves its result there (caption.py:166-167)
+            with open(captions_path, "w") as f:
+                json.dump(captions, f)
+        thumbnails = [None] * num_objs
+
+        vis_models = [None] * num_objs                             # created lazily once the task is known (:167-168)
+        objs = [ObjectModel(captions[k], vis_models[k], phys_models[k], init_poses[k], thumbnails[k], k) for k in range(num_objs)]
+        self.scene_model = SceneModel(cfg.scene_centre, objs, objs[0], rgbs, depths, opt_cam_poses, intrinsics, masks,
+                                      cfg.scene_phys_bounds, cfg.scene_type)
+
+    def determine_movable_obj(self, user_instr):
+        """reference :179-193 -> (movable_obj, movable_idx)"""
+        obj_captions = [obj.name for obj in self.scene_model.objs]
+        movable_idx = self.lang_model.get_movable_obj_idx(user_instr, obj_captions)
+        return self.scene_model.objs[movable_idx], movable_idx
+
+    def determine_relevant_objs(self, norm_caption, movable_obj_idx):
+        """reference :195-214: the objects that are not distractors."""
+        obj_captions = [obj.name for obj in self.scene_model.objs]
+        relevant_idxs = self.lang_model.get_relevant_obj_idxs(norm_caption, obj_captions, movable_obj_idx)
+        if len(relevant_idxs) == 0:
+            raise RuntimeError("Error: None of the captioned objects were determined to be relevant.")
+        return [self.scene_model.objs[idx] for idx in relevant_idxs]
+
+    def interpret_user_instr(self, user_instr, goal_caption=None, norm_captions=None):
+        """reference dream2real.py:216-280 -> TaskModel."""
+        from .scene_model import TaskModel
+        cfg = self.cfg
+        if self.scene_model is None:
+            raise RuntimeError("Must call build_scene_model() first before receiving user instructions")
+        if self.lang_model is None:
+            raise RuntimeError("interpret_user_instr needs lang_model= (e.g. CachedLangModel(path)): no LLM is called from here")
+        if goal_caption is None:
+            goal_caption, norm_caption = self.lang_model.parse_instr(user_instr)
+            norm_captions = [norm_caption]
+        movable_obj, movable_obj_idx = self.determine_movable_obj(user_instr)
+        relevant_objs = self.determine_relevant_objs(goal_caption, movable_obj_idx)
+
+        # before the visual models, as in the reference (:244-250)
+        if cfg.lazy_phys_mods:
+            [bground_phys, movable_phys], [bground_init_pose, movable_init_pose] = TaskModel.create_lazy_phys_mods(
+                self.scene_model, movable_obj, cfg.scene_phys_bounds, save_dir=os.path.join(self.data_dir, "phys_mod/"), embodied=cfg.embodied,
+                vis=False, use_cache=cfg.use_cache_phys, use_phys_tsdf=cfg.use_phys_tsdf, use_vis_pcds=cfg.use_vis_pcds,
+                single_view_idx=cfg.single_view_idx, ctx=self.ctx, phys_backend=cfg.phys_backend)
+
+        movable_obj.vis_model = TaskModel.create_movable_vis_model(
+            self.scene_model, movable_obj, self.out_scene_bound_masks, os.path.join(self.data_dir, "movable_vis_mod/"),
+            use_vis_pcds=cfg.use_vis_pcds, pcds_type=cfg.pcds_type, single_view_idx=cfg.single_view_idx, use_cache=cfg.use_cache_vis,
+            data_dir=self.data_dir, ctx=self.ctx)
+        task_bground_obj, task_bground_masks = TaskModel.create_task_bground_obj(
+            self.scene_model, movable_obj, relevant_objs, self.out_scene_bound_masks, os.path.join(self.data_dir, "task_bground_vis_mod/"),
+            use_vis_pcds=cfg.use_vis_pcds, pcds_type=cfg.pcds_type, single_view_idx=cfg.single_view_idx,
+            render_distractors=cfg.render_distractors, use_cache=cfg.use_cache_vis, data_dir=self.data_dir, ctx=self.ctx)
+
+        if cfg.lazy_phys_mods:                                                                                    # :274-277
+            movable_obj.phys_model = movable_phys
+            movable_obj.pose = movable_init_pose
+            task_bground_obj.phys_model = bground_phys
+
+        return TaskModel(user_instr, goal_caption, norm_captions, self.scene_model, movable_obj, task_bground_obj, task_bground_masks,
+                         self.topdown)
 
     def dream_best_pose(self, task_model):
         """-> (best_pose [4,4], pose_batch [N,16], pose_scores [N]) as torch tensors; writes goal_pose.txt,

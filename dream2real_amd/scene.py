@@ -24,6 +24,9 @@ LENS_PERSPECTIVE, LENS_OPENCV = 0, 1      # d2r.h D2R_LENS_*
 # the OpenCV coefficients (k1, k2, p1, p2) every demo config of the reference writes into the transforms its NeRFs are
 # trained from (configs/shopping_demo.json:51-56, shelf_demo.json:51-56; reconstruction/train_ngp.py:171-180)
 DEMO_LENS = (0.096692, -0.166479, -0.000194, 0.002049)
+# the 1280 x 720 RealSense intrinsics the reference builds every scene with (vision_3d/camera_info.py; the same numbers as the
+# `camera` group of its configs and View.from_training_view's defaults)
+INTRINSICS_REALSENSE_1280 = np.array([[924.66912, 0.0, 654.51953], [0.0, 926.49735, 355.18523], [0.0, 0.0, 1.0]])
 DT = np.float32(math.sqrt(3.0) / 1024.0)   # constant march step at aabb_scale 1
 
 

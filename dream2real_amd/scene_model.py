@@ -99,10 +99,10 @@ class TaskModel:
 
     @staticmethod
     def create_lazy_phys_mods(scene_model, movable_obj, scene_bounds, save_dir, embodied=False, vis=False, use_cache=False, use_phys_tsdf=True,
-                              use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None):
+                              use_vis_pcds=False, single_view_idx=0, *, ctx=None, convexify=None, phys_backend="hulls"):
         return physics_utils.create_lazy_phys_mods(scene_model, movable_obj, scene_bounds, save_dir, embodied=embodied, vis=vis, use_cache=use_cache,
                                                    use_phys_tsdf=use_phys_tsdf, use_vis_pcds=use_vis_pcds, single_view_idx=single_view_idx, ctx=ctx,
-                                                   convexify=convexify)
+                                                   convexify=convexify, phys_backend=phys_backend)
 
     def free_visual_models(self):
         self.task_bground_obj.vis_model = None

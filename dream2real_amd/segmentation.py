@@ -59,6 +59,30 @@ def refine_masks(raw_masks, depths, T_WC, intrinsics, out_scene_bound_masks, sce
     return refined
 
 
+def labels_from_census(counts):
+    """The object count of build_scene_model (reference dream2real.py:139-144) from per-frame label counts [N,256] (or totals
+    [256]): labels = the labels some pixel carries, num_objs = their number without 255 (out of scene).  ObjectModel.mask_idx =
+    obj_idx assumes the labels below 255 are exactly 0 .. num_objs - 1; anything else is a ValueError naming the first missing
+    label.  -> (labels int array, num_objs)."""
+    totals = np.asarray(counts, np.uint64).reshape(-1, 256).sum(axis=0)
+    labels = np.nonzero(totals)[0]
+    num_objs = len(labels) - int(255 in labels)
+    objs = labels[labels != 255]
+    if not np.array_equal(objs, np.arange(num_objs)):
+        missing = int(np.setdiff1d(np.arange(int(objs.max()) + 1), objs)[0])
+        raise ValueError(f"label census: the masks carry the labels {objs.tolist()} but not {missing}; object k must carry label k "
+                         f"(labels 0 .. {num_objs - 1} for {num_objs} objects, 255 outside the scene)")
+    return labels, num_objs
+
+
+def label_census(masks, *, ctx):
+    """uint8 label images [N,H,W] -> (labels, num_objs, counts uint32 [N,256]): one d2r_masks_census call in place of
+    torch.unique over all frames; counts[f, k] > 0 says frame f sees object k."""
+    counts = _lib.masks_census(ctx, _np(masks).astype(np.uint8))
+    labels, num_objs = labels_from_census(counts)
+    return labels, num_objs, counts
+
+
 def load_cached_masks(out_dir, n):
     """segment_associate's cache branch: <out_dir>/XMem_masks/rgb_%04d.png for n frames -> uint8 [n,H,W]."""
     mask_dir = os.path.join(out_dir, "XMem_masks")

@@ -802,8 +802,13 @@ D2R_API int d2r_masks_components(d2r_ctx *ctx, const uint8_t *mask_u8, const uin
 D2R_API int d2r_masks_lut(d2r_ctx *ctx, const uint8_t *masks_u8, const uint8_t *oob_u8, uint32_t n, uint32_t w, uint32_t h,
                           const uint8_t *lut, uint8_t *out_u8, uint8_t *alpha_out_u8);
 
-/* Device-event times of the last d2r_scene_bound_masks / d2r_masks_prune on this context: ms_out host [3] = upload, kernels,
- * download, in milliseconds. */
+/* The label census of build_scene_model (reference dream2real.py:141-144, torch.unique over all frames): counts_out host
+ * [n][256] uint32, counts_out[f][l] = the number of pixels of frame f that carry label l.  Any w, h and n the batch calls take;
+ * a row need not be a multiple of any load width.  Integer sums only: the result does not depend on the order of the adds. */
+D2R_API int d2r_masks_census(d2r_ctx *ctx, const uint8_t *masks_u8, uint32_t n, uint32_t w, uint32_t h, uint32_t *counts_out);
+
+/* Device-event times of the last d2r_scene_bound_masks / d2r_masks_prune / d2r_masks_census on this context: ms_out host [3] =
+ * upload, kernels, download, in milliseconds. */
 D2R_API int d2r_masks_get_timing(d2r_ctx *ctx, double *ms_out);
 
 #ifdef __cplusplus
