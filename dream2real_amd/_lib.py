@@ -11,25 +11,93 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libd2r.so")
 ABI_VERSION = 10        # D2R_ABI_VERSION of include/d2r.h this binding was written against
 
-EXPORTS = [
-    "d2r_abi_version", "d2r_ctx_create", "d2r_ctx_destroy", "d2r_ctx_set_stream", "d2r_ctx_synchronize",
-    "d2r_last_error", "d2r_nerf_create", "d2r_nerf_destroy", "d2r_render", "d2r_nerf_eval_points",
-    "d2r_set_background", "d2r_render_composite", "d2r_clip_create", "d2r_clip_destroy",
-    "d2r_clip_score_frames", "d2r_clip_preprocess", "d2r_clip_embed_pixels", "d2r_render_score",
-    "d2r_get_render_stats", "d2r_collect_render_stats", "d2r_ctx_set_option", "d2r_get_timing", "d2r_text_create",
-    "d2r_text_destroy", "d2r_text_encode", "d2r_comm_get_unique_id", "d2r_comm_init", "d2r_comm_destroy",
-    "d2r_allgather_scores", "d2r_phys_create", "d2r_phys_destroy", "d2r_phys_check", "d2r_nerf_load_ingp", "d2r_lens_undistort_view",
-    "d2r_rectify_background_depth", "d2r_ingp_inspect", "d2r_render_score_host", "d2r_png_write", "d2r_png_write_batch",
-    "d2r_png_read_batch", "d2r_png_size", "d2r_savetxt", "d2r_ingp_validate", "d2r_debug_gemm_fp8", "d2r_ctx_get_option", "d2r_png_write_batch_bg",
-    "d2r_pcd_create", "d2r_pcd_destroy", "d2r_pcd_render", "d2r_pcd_render_score_host",
-    "d2r_tsdf_create", "d2r_tsdf_destroy", "d2r_tsdf_integrate", "d2r_tsdf_read_voxels", "d2r_tsdf_extract", "d2r_obj_write",
-    "d2r_tsdf_grid", "d2r_tsdf_touch_bits", "d2r_tsdf_solid_points",
-    "d2r_sdfphys_create", "d2r_sdfphys_destroy", "d2r_sdfphys_check", "d2r_sdfphys_get_timing",
-    "d2r_png_write_channels", "d2r_png_info", "d2r_png_read_grey", "d2r_png_read_rgb",
-    "d2r_scene_bound_masks", "d2r_masks_prune", "d2r_masks_components", "d2r_masks_lut", "d2r_masks_get_timing",
-    "d2r_pcd_build", "d2r_pcd_size", "d2r_pcd_read", "d2r_pcd_build_get_timing",
-    "d2r_masks_census",
-]
+# One line per function of include/d2r.h: name: (restype, (argtypes...)).  The rule: a scalar (int, int32_t, uint32_t, int64_t,
+# uint64_t, size_t, float, double) is its exact ctypes type; `const char *`, as a parameter or a return type, is c_char_p; every
+# other pointer (char * output buffers, arrays, pointers to structs, handles, pointers to handles) is c_void_p, which takes None,
+# byref(...), ctypes arrays, bytes and c_void_p, so NULL and wrong-handle arguments still reach the library's own checks; a void
+# return is None.  tests/test_abi.py compares this table and the struct mirrors below with the header.
+_int, _u32, _i64, _u64, _size, _f32, _f64, _str, _ptr = (C.c_int, C.c_uint32, C.c_int64, C.c_uint64, C.c_size_t, C.c_float, C.c_double,
+                                                          C.c_char_p, C.c_void_p)
+PROTOTYPES = {
+    "d2r_abi_version": (_int, ()),
+    "d2r_ctx_create": (_int, (_int, _ptr)),
+    "d2r_ctx_destroy": (None, (_ptr,)),
+    "d2r_ctx_set_stream": (_int, (_ptr, _ptr)),
+    "d2r_ctx_synchronize": (_int, (_ptr,)),
+    "d2r_last_error": (_str, (_ptr,)),
+    "d2r_nerf_create": (_int, (_ptr, _ptr, _ptr)),
+    "d2r_nerf_destroy": (None, (_ptr,)),
+    "d2r_nerf_load_ingp": (_int, (_ptr, _ptr, _size, _ptr, _ptr, _ptr, _u32)),
+    "d2r_ingp_inspect": (_int, (_ptr, _size, _ptr, _size, _ptr)),
+    "d2r_ingp_validate": (_int, (_ptr, _size, _ptr)),
+    "d2r_render": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr)),
+    "d2r_lens_undistort_view": (_int, (_ptr, _ptr, _ptr)),
+    "d2r_nerf_eval_points": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_set_background": (_int, (_ptr, _ptr, _ptr, _ptr)),
+    "d2r_rectify_background_depth": (_int, (_ptr, _ptr, _int, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr)),
+    "d2r_render_composite": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_clip_create": (_int, (_ptr, _ptr, _ptr, _size, _ptr)),
+    "d2r_clip_destroy": (None, (_ptr,)),
+    "d2r_clip_score_frames": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _int, _ptr, _u32, _f32, _ptr, _ptr)),
+    "d2r_clip_preprocess": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _int, _ptr)),
+    "d2r_clip_embed_pixels": (_int, (_ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_debug_gemm_fp8": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_text_create": (_int, (_ptr, _ptr, _ptr, _size, _ptr)),
+    "d2r_text_destroy": (None, (_ptr,)),
+    "d2r_text_encode": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _ptr)),
+    "d2r_render_score": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr)),
+    "d2r_render_score_host": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr, _ptr)),
+    "d2r_png_write": (_int, (_ptr, _u32, _u32, _str, _int)),
+    "d2r_png_write_batch": (_int, (_ptr, _u32, _u32, _u32, _str, _u32, _int, _int)),
+    "d2r_png_write_batch_bg": (_int, (_ptr, _u32, _u32, _u32, _ptr, _str, _u32, _int)),
+    "d2r_png_read_batch": (_int, (_str, _ptr, _u32, _u32, _u32, _u32, _ptr, _int)),
+    "d2r_png_size": (_int, (_str, _ptr, _ptr)),
+    "d2r_savetxt": (_int, (_str, _ptr, _u64, _u64, _int)),
+    "d2r_get_render_stats": (_int, (_ptr, _ptr)),
+    "d2r_collect_render_stats": (_int, (_ptr, _u32)),
+    "d2r_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_ctx_set_option": (_int, (_ptr, _str, _i64)),
+    "d2r_ctx_get_option": (_int, (_ptr, _str, _ptr)),
+    "d2r_comm_get_unique_id": (_int, (_ptr,)),
+    "d2r_comm_init": (_int, (_ptr, _ptr, _int, _int)),
+    "d2r_comm_destroy": (_int, (_ptr,)),
+    "d2r_allgather_scores": (_int, (_ptr, _ptr, _size, _ptr)),
+    "d2r_phys_create": (_int, (_ptr, _ptr, _ptr, _u32, _ptr, _ptr, _u32, _ptr)),
+    "d2r_phys_destroy": (None, (_ptr,)),
+    "d2r_phys_check": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_pcd_create": (_int, (_ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_pcd_destroy": (None, (_ptr,)),
+    "d2r_pcd_render": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_pcd_render_score_host": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr)),
+    "d2r_pcd_build": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _f64, _ptr, _u32, _ptr, _u32, _ptr)),
+    "d2r_pcd_size": (_int, (_ptr, _ptr)),
+    "d2r_pcd_read": (_int, (_ptr, _ptr, _ptr, _ptr)),
+    "d2r_pcd_build_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_tsdf_create": (_int, (_ptr, _ptr, _f32, _f32, _ptr)),
+    "d2r_tsdf_destroy": (None, (_ptr,)),
+    "d2r_tsdf_integrate": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _u32)),
+    "d2r_tsdf_read_voxels": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_tsdf_extract": (_int, (_ptr, _f32, _ptr, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_obj_write": (_int, (_str, _ptr, _u32, _ptr, _u32, _ptr)),
+    "d2r_tsdf_grid": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_tsdf_touch_bits": (_int, (_ptr, _f32, _f32, _ptr)),
+    "d2r_tsdf_solid_points": (_int, (_ptr, _f32, _ptr, _ptr)),
+    "d2r_sdfphys_create": (_int, (_ptr, _ptr, _ptr, _f32, _ptr, _u32, _ptr, _u32, _ptr)),
+    "d2r_sdfphys_destroy": (None, (_ptr,)),
+    "d2r_sdfphys_check": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_sdfphys_get_timing": (_int, (_ptr, _ptr, _ptr)),
+    "d2r_png_write_channels": (_int, (_ptr, _u32, _u32, _u32, _str, _int)),
+    "d2r_png_info": (_int, (_str, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_png_read_rgb": (_int, (_str, _u32, _u32, _ptr)),
+    "d2r_png_read_grey": (_int, (_str, _u32, _u32, _u32, _ptr)),
+    "d2r_scene_bound_masks": (_int, (_ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _u32, _ptr, _ptr)),
+    "d2r_masks_prune": (_int, (_ptr, _int, _ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _u32, _ptr)),
+    "d2r_masks_components": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr)),
+    "d2r_masks_lut": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr)),
+    "d2r_masks_census": (_int, (_ptr, _ptr, _u32, _u32, _u32, _ptr)),
+    "d2r_masks_get_timing": (_int, (_ptr, _ptr)),
+}
+EXPORTS = list(PROTOTYPES)
 
 
 class D2RError(RuntimeError):
@@ -127,18 +195,9 @@ def load() -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    lib.d2r_last_error.restype = C.c_char_p
-    lib.d2r_last_error.argtypes = [C.c_void_p]
-    lib.d2r_ctx_destroy.restype = None
-    lib.d2r_nerf_destroy.restype = None
-    lib.d2r_clip_destroy.restype = None
-    lib.d2r_text_destroy.restype = None
-    lib.d2r_phys_destroy.restype = None
-    lib.d2r_pcd_destroy.restype = None
-    lib.d2r_tsdf_destroy.restype = None
-    lib.d2r_sdfphys_destroy.restype = None
-    for name in EXPORTS:
-        getattr(lib, name)          # every declared symbol must be exported
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)     # every declared symbol must be exported
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.d2r_abi_version() != ABI_VERSION:
         raise D2RError("libd2r.so ABI version mismatch")
     _lib = lib
@@ -149,7 +208,6 @@ def ingp_inspect(data: bytes) -> str:
     """d2r_ingp_inspect: the msgpack tree of a snapshot as text, each leaf marked as read / ignored by the loader,
     plus the sizes the loader derives (host only: works without a GPU)."""
     lib = load()
-    lib.d2r_ingp_inspect.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     need = C.c_size_t(0)
     check(lib.d2r_ingp_inspect(data, len(data), None, 0, C.byref(need)))
     buf = C.create_string_buffer(need.value)
@@ -161,7 +219,7 @@ def png_write(rgb, path: str, level: int = -1):
     """d2r_png_write: one uint8 [h,w,3] image -> an RGB PNG file (host only)."""
     a = np.ascontiguousarray(rgb, np.uint8)
     assert a.ndim == 3 and a.shape[2] == 3
-    check(load().d2r_png_write(ptr(a), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]), os.fsencode(path), C.c_int(level)))
+    check(load().d2r_png_write(ptr(a), a.shape[1], a.shape[0], os.fsencode(path), level))
 
 
 def png_write_batch(frames, out_dir: str, first_index: int = 0, threads: int = 0, level: int = -1):
@@ -169,8 +227,7 @@ def png_write_batch(frames, out_dir: str, first_index: int = 0, threads: int = 0
     for the duration of the call)."""
     a = np.ascontiguousarray(frames, np.uint8)
     assert a.ndim == 4 and a.shape[3] == 3
-    check(load().d2r_png_write_batch(ptr(a), C.c_uint32(a.shape[0]), C.c_uint32(a.shape[2]), C.c_uint32(a.shape[1]),
-                                     os.fsencode(out_dir), C.c_uint32(first_index), C.c_int(threads), C.c_int(level)))
+    check(load().d2r_png_write_batch(ptr(a), a.shape[0], a.shape[2], a.shape[1], os.fsencode(out_dir), first_index, threads, level))
 
 
 def png_write_batch_bg(frames, background, out_dir: str, first_index: int = 0, threads: int = 0):
@@ -179,8 +236,7 @@ def png_write_batch_bg(frames, background, out_dir: str, first_index: int = 0, t
     a = np.ascontiguousarray(frames, np.uint8)
     b = np.ascontiguousarray(background, np.uint8)
     assert a.ndim == 4 and a.shape[3] == 3 and b.shape == a.shape[1:]
-    check(load().d2r_png_write_batch_bg(ptr(a), C.c_uint32(a.shape[0]), C.c_uint32(a.shape[2]), C.c_uint32(a.shape[1]), ptr(b),
-                                        os.fsencode(out_dir), C.c_uint32(first_index), C.c_int(threads)))
+    check(load().d2r_png_write_batch_bg(ptr(a), a.shape[0], a.shape[2], a.shape[1], ptr(b), os.fsencode(out_dir), first_index, threads))
 
 
 def png_write_channels(pixels, path: str, level: int = -1):
@@ -190,8 +246,7 @@ def png_write_channels(pixels, path: str, level: int = -1):
         a = a[:, :, None]
     if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
         raise ValueError(f"expected [h,w], [h,w,3] or [h,w,4], got shape {a.shape}")
-    check(load().d2r_png_write_channels(ptr(a), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]), C.c_uint32(a.shape[2]), os.fsencode(path),
-                                        C.c_int(level)))
+    check(load().d2r_png_write_channels(ptr(a), a.shape[1], a.shape[0], a.shape[2], os.fsencode(path), level))
 
 
 def png_info(path: str):
@@ -205,7 +260,7 @@ def png_read_rgb(path: str, size=None) -> np.ndarray:
     """d2r_png_read_rgb: one 8-bit PNG -> uint8 [h,w,3] in R, G, B order (grey replicated, alpha dropped)."""
     w, h = size or png_info(path)[:2]
     out = np.empty((h, w, 3), np.uint8)
-    check(load().d2r_png_read_rgb(os.fsencode(path), C.c_uint32(w), C.c_uint32(h), ptr(out)))
+    check(load().d2r_png_read_rgb(os.fsencode(path), w, h, ptr(out)))
     return out
 
 
@@ -213,7 +268,7 @@ def png_read_grey(path: str, bits: int = 8, size=None) -> np.ndarray:
     """d2r_png_read_grey: a grey PNG of `bits` (8 or 16) -> uint8 / uint16 [h,w].  `size` = (w, h) expected, default the file's."""
     w, h = size or png_info(path)[:2]
     out = np.empty((h, w), np.uint16 if bits == 16 else np.uint8)
-    check(load().d2r_png_read_grey(os.fsencode(path), C.c_uint32(bits), C.c_uint32(w), C.c_uint32(h), ptr(out)))
+    check(load().d2r_png_read_grey(os.fsencode(path), bits, w, h, ptr(out)))
     return out
 
 
@@ -233,8 +288,7 @@ def png_read_batch(in_dir: str, n: int = 0, first_index: int = 0, threads: int =
         return np.empty((0, 0, 0, 3), np.uint8)
     w, h = size or png_size(os.path.join(in_dir, f"cb_rgb_{int(idx[0]) if idx is not None else first_index:04d}.png"))
     out = np.empty((n, h, w, 3), np.uint8)
-    check(load().d2r_png_read_batch(os.fsencode(in_dir), ptr(idx), C.c_uint32(first_index), C.c_uint32(n), C.c_uint32(w),
-                                    C.c_uint32(h), ptr(out), C.c_int(threads)))
+    check(load().d2r_png_read_batch(os.fsencode(in_dir), ptr(idx), first_index, n, w, h, ptr(out), threads))
     return out
 
 
@@ -246,7 +300,7 @@ def savetxt(path: str, array):
         raise ValueError(f"Expected 1D or 2D array, got {a.ndim}D array instead")
     a = np.ascontiguousarray(a, np.float64)
     rows, cols = (a.shape[0], 1) if a.ndim == 1 else a.shape
-    check(load().d2r_savetxt(os.fsencode(path), ptr(a), C.c_uint64(rows), C.c_uint64(cols), C.c_int(0)))
+    check(load().d2r_savetxt(os.fsencode(path), ptr(a), rows, cols, 0))
 
 
 def obj_write(path: str, vertices, triangles, keep=None):
@@ -256,13 +310,12 @@ def obj_write(path: str, vertices, triangles, keep=None):
     t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
     k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
     assert k is None or k.shape[0] == t.shape[0]
-    check(load().d2r_obj_write(os.fsencode(path), ptr(v), C.c_uint32(v.shape[0]), ptr(t), C.c_uint32(t.shape[0]), ptr(k)))
+    check(load().d2r_obj_write(os.fsencode(path), ptr(v), v.shape[0], ptr(t), t.shape[0], ptr(k)))
 
 
-def _h(ctx) -> C.c_void_p:
+def _h(ctx):
     """The d2r_ctx pointer of an engine.Context (or a raw handle)."""
-    h = getattr(ctx, "h", ctx)
-    return h if isinstance(h, C.c_void_p) else C.c_void_p(h)
+    return getattr(ctx, "h", ctx)
 
 
 def _frames(a, dtype, name):
@@ -284,8 +337,7 @@ def scene_bound_masks(ctx, depth_u16, poses, K, bounds, window: int = 50, return
     b = np.array(bounds, np.float64).reshape(6)          # a copy: the caller's bounds stay as they are
     out = np.empty((n, h, w), np.uint8)
     raw = np.empty((n, h, w), np.uint8) if return_raw else None
-    check(load().d2r_scene_bound_masks(_h(ctx), ptr(d), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(T), ptr(Kd), ptr(b),
-                                       C.c_uint32(window), ptr(out), ptr(raw)), _h(ctx))
+    check(load().d2r_scene_bound_masks(_h(ctx), ptr(d), n, w, h, ptr(T), ptr(Kd), ptr(b), window, ptr(out), ptr(raw)), _h(ctx))
     return (out, raw) if return_raw else out
 
 
@@ -305,8 +357,7 @@ def masks_prune(ctx, mode: int, masks, depth_u16=None, oob=None, poses=None, K=N
     Kd = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)
     c = None if centre is None else np.ascontiguousarray(centre, np.float64).reshape(3)
     out = np.empty((n, h, w), np.uint8)
-    check(load().d2r_masks_prune(_h(ctx), C.c_int(mode), ptr(m), ptr(d), ptr(o), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(T),
-                                 ptr(Kd), ptr(c), C.c_uint32(min_area), ptr(out)), _h(ctx))
+    check(load().d2r_masks_prune(_h(ctx), mode, ptr(m), ptr(d), ptr(o), n, w, h, ptr(T), ptr(Kd), ptr(c), min_area, ptr(out)), _h(ctx))
     return out
 
 
@@ -318,8 +369,7 @@ def masks_components(ctx, mask, depth_u16):
         raise ValueError("mask and depth_u16 must be [h, w] of one shape")
     h, w = m.shape
     keys, area, sums = np.empty((h, w), np.uint32), np.empty((h, w), np.uint32), np.empty((h, w, 4), np.uint64)
-    check(load().d2r_masks_components(_h(ctx), ptr(m), ptr(d), C.c_uint32(w), C.c_uint32(h), ptr(keys), ptr(area), ptr(sums)),
-          _h(ctx))
+    check(load().d2r_masks_components(_h(ctx), ptr(m), ptr(d), w, h, ptr(keys), ptr(area), ptr(sums)), _h(ctx))
     return keys, area, sums
 
 
@@ -335,8 +385,7 @@ def masks_lut(ctx, masks, lut, oob=None, alpha: bool = False):
         raise ValueError("lut must have 256 entries")
     out = np.empty((n, h, w), np.uint8)
     al = np.empty((n, h, w), np.uint8) if alpha else None
-    check(load().d2r_masks_lut(_h(ctx), ptr(m), ptr(o), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(t), ptr(out), ptr(al)),
-          _h(ctx))
+    check(load().d2r_masks_lut(_h(ctx), ptr(m), ptr(o), n, w, h, ptr(t), ptr(out), ptr(al)), _h(ctx))
     return (out, al) if alpha else out
 
 
@@ -345,7 +394,7 @@ def masks_census(ctx, masks):
     m = _frames(masks, np.uint8, "masks")
     n, h, w = m.shape
     out = np.empty((n, 256), np.uint32)
-    check(load().d2r_masks_census(_h(ctx), ptr(m), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(out)), _h(ctx))
+    check(load().d2r_masks_census(_h(ctx), ptr(m), n, w, h, ptr(out)), _h(ctx))
     return out
 
 
@@ -374,8 +423,8 @@ def pcd_build(ctx, rgb, depth_u16, labels, cam_poses, K, bounds, voxel: float, v
     vw = np.ascontiguousarray(views, np.uint32).reshape(-1)
     ids = np.ascontiguousarray(obj_ids, np.uint8).reshape(-1)
     out = (C.c_void_p * max(1, ids.size))()
-    check(load().d2r_pcd_build(_h(ctx), ptr(c), ptr(d), ptr(m), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), ptr(T), ptr(Kd), ptr(b),
-                               C.c_double(voxel), ptr(vw), C.c_uint32(vw.size), ptr(ids), C.c_uint32(ids.size), out), _h(ctx))
+    check(load().d2r_pcd_build(_h(ctx), ptr(c), ptr(d), ptr(m), n, w, h, ptr(T), ptr(Kd), ptr(b), voxel, ptr(vw), vw.size, ptr(ids),
+                               ids.size, out), _h(ctx))
     return [C.c_void_p(out[i]) for i in range(ids.size)]
 
 
@@ -399,9 +448,7 @@ def ingp_validate(data: bytes) -> IngpInfo:
     """d2r_ingp_validate: raises D2RError with the loader's message (naming the key) when d2r_nerf_load_ingp would refuse
     the snapshot; returns what the loader would report about it otherwise.  Host only."""
     info = IngpInfo()
-    lib = load()
-    lib.d2r_ingp_validate.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
-    check(lib.d2r_ingp_validate(data, len(data), C.byref(info)))
+    check(load().d2r_ingp_validate(data, len(data), C.byref(info)))
     return info
 
 

@@ -28,7 +28,7 @@ class Context:
     def __init__(self, device: int = 0):
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.d2r_ctx_create(C.c_int(device), C.byref(h)))
+        _lib.check(self.lib.d2r_ctx_create(device, C.byref(h)))
         self.h = h
         self.device = device
 
@@ -47,13 +47,13 @@ class Context:
         _lib.check(rc, self.h)
 
     def set_stream(self, hip_stream_ptr: int):
-        self.check(self.lib.d2r_ctx_set_stream(self.h, C.c_void_p(hip_stream_ptr)))
+        self.check(self.lib.d2r_ctx_set_stream(self.h, hip_stream_ptr))
 
     def synchronize(self):
         self.check(self.lib.d2r_ctx_synchronize(self.h))
 
     def set_option(self, key: str, value: int):
-        self.check(self.lib.d2r_ctx_set_option(self.h, key.encode(), C.c_int64(value)))
+        self.check(self.lib.d2r_ctx_set_option(self.h, key.encode(), value))
 
     def get_option(self, key: str) -> int:
         v = C.c_int64(0)
@@ -62,7 +62,7 @@ class Context:
 
     def render_stats(self, collect_K: int | None = None) -> dict:
         if collect_K is not None:
-            self.check(self.lib.d2r_collect_render_stats(self.h, C.c_uint32(collect_K)))
+            self.check(self.lib.d2r_collect_render_stats(self.h, collect_K))
         s = _lib.RenderStats()
         self.check(self.lib.d2r_get_render_stats(self.h, C.byref(s)))
         return {"rays_total": s.rays_total, "rays_alive": s.rays_alive, "samples": s.samples,
@@ -84,15 +84,14 @@ class Context:
     def comm_init(self, id_blob: bytes | None, rank: int, world: int):
         if id_blob is not None:
             assert len(id_blob) == _lib.COMM_ID_BYTES
-        self.check(self.lib.d2r_comm_init(self.h, id_blob, C.c_int(rank), C.c_int(world)))
+        self.check(self.lib.d2r_comm_init(self.h, id_blob, rank, world))
 
     def comm_destroy(self):
         self.check(self.lib.d2r_comm_destroy(self.h))
 
     def allgather_scores(self, local_dev_ptr: int, n_local: int, global_dev_ptr: int):
         """d2r_allgather_scores: [n_local] fp32 on every rank -> [world][n_local], async on the stream."""
-        self.check(self.lib.d2r_allgather_scores(self.h, C.c_void_p(local_dev_ptr), C.c_size_t(n_local),
-                                                 C.c_void_p(global_dev_ptr)))
+        self.check(self.lib.d2r_allgather_scores(self.h, local_dev_ptr, n_local, global_dev_ptr))
 
     def set_background(self, view: View, bg_rgba: np.ndarray, bg_depth: np.ndarray):
         a = np.ascontiguousarray(bg_rgba, np.float32)
@@ -123,9 +122,7 @@ class Context:
         out = np.empty((height, width), np.float32)
         mo = np.empty((height, width), np.uint8) if (return_mask and m is not None) else None
         self.check(self.lib.d2r_rectify_background_depth(
-            self.h, _lib.ptr(d), C.c_int(1 if d.dtype == np.float16 else 0), _lib.ptr(m) if m is not None else None,
-            C.c_uint32(sw), C.c_uint32(sh), C.c_uint32(width), C.c_uint32(height), _lib.ptr(out),
-            _lib.ptr(mo) if mo is not None else None))
+            self.h, _lib.ptr(d), 1 if d.dtype == np.float16 else 0, _lib.ptr(m), sw, sh, width, height, _lib.ptr(out), _lib.ptr(mo)))
         return (out, mo) if return_mask else out
 
 
@@ -199,8 +196,7 @@ class Testbed:
         info = _lib.IngpInfo()
         cap = 4096
         views = (_lib.IngpView * cap)()
-        ctx.check(ctx.lib.d2r_nerf_load_ingp(ctx.h, _lib.ptr(buf), C.c_size_t(buf.size), C.byref(h), C.byref(info), views,
-                                             C.c_uint32(cap)))
+        ctx.check(ctx.lib.d2r_nerf_load_ingp(ctx.h, _lib.ptr(buf), buf.size, C.byref(h), C.byref(info), views, cap))
         tv = [dict(fx=float(v.fx), fy=float(v.fy), cx=float(v.cx), cy=float(v.cy), w=int(v.w), h=int(v.h),
                    lens=tuple(float(x) for x in v.lens_params) if v.lens_mode == LENS_OPENCV else None)
               for v in views[: info.n_views_written]]
@@ -274,8 +270,7 @@ class Testbed:
         depth = np.empty((n, height, width), np.float32)
         v = _lib.view_c(self.view(width, height))
         ns = C.c_uint64(0)
-        self.ctx.check(self.ctx.lib.d2r_render(self.ctx.h, self.h, C.byref(v), _lib.ptr(cams), C.c_uint32(n),
-                                               _lib.ptr(rgba), _lib.ptr(depth), C.byref(ns)))
+        self.ctx.check(self.ctx.lib.d2r_render(self.ctx.h, self.h, C.byref(v), _lib.ptr(cams), n, _lib.ptr(rgba), _lib.ptr(depth), C.byref(ns)))
         self.last_samples = int(ns.value)
         return rgba, depth
 
@@ -283,8 +278,7 @@ class Testbed:
         p = np.ascontiguousarray(xyz, np.float32)
         d = np.ascontiguousarray(dirs, np.float32)
         out = np.empty((p.shape[0], 4), np.float32)
-        self.ctx.check(self.ctx.lib.d2r_nerf_eval_points(self.ctx.h, self.h, _lib.ptr(p), _lib.ptr(d),
-                                                         C.c_uint32(p.shape[0]), _lib.ptr(out)))
+        self.ctx.check(self.ctx.lib.d2r_nerf_eval_points(self.ctx.h, self.h, _lib.ptr(p), _lib.ptr(d), p.shape[0], _lib.ptr(out)))
         return out
 
     def render_composite(self, view: View, obj_pose_now, cam_pose, obj_poses) -> np.ndarray:
@@ -295,8 +289,7 @@ class Testbed:
         K = p.shape[0]
         frames = np.empty((K, view.height, view.width, 3), np.uint8)
         v = _lib.view_c(view)
-        self.ctx.check(self.ctx.lib.d2r_render_composite(self.ctx.h, self.h, C.byref(v), _lib.ptr(a), _lib.ptr(c),
-                                                         _lib.ptr(p), C.c_uint32(K), _lib.ptr(frames)))
+        self.ctx.check(self.ctx.lib.d2r_render_composite(self.ctx.h, self.h, C.byref(v), _lib.ptr(a), _lib.ptr(c), _lib.ptr(p), K, _lib.ptr(frames)))
         return frames
 
 
@@ -310,7 +303,7 @@ class ClipScorer:
         desc = _lib.ClipDesc(cfg["image_size"], cfg["patch_size"], cfg["hidden_size"], cfg["num_layers"],
                              cfg["num_heads"], cfg["mlp"], cfg["proj"])
         h = C.c_void_p()
-        ctx.check(ctx.lib.d2r_clip_create(ctx.h, C.byref(desc), _lib.ptr(blob), C.c_size_t(blob.size), C.byref(h)))
+        ctx.check(ctx.lib.d2r_clip_create(ctx.h, C.byref(desc), _lib.ptr(blob), blob.size, C.byref(h)))
         self.h = h
         self.logit_scale = float(np.exp(np.float32(state_dict.get("logit_scale", 4.6052))))
 
@@ -333,8 +326,7 @@ class ClipScorer:
         logits = np.empty((n, Cn), np.float32)
         emb = np.empty((n, self.cfg["proj"]), np.float32) if return_embeds else None
         self.ctx.check(self.ctx.lib.d2r_clip_score_frames(
-            self.ctx.h, self.h, _lib.ptr(f), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), C.c_int(int(rot90)),
-            _lib.ptr(t), C.c_uint32(Cn), C.c_float(self.logit_scale), _lib.ptr(logits), _lib.ptr(emb)))
+            self.ctx.h, self.h, _lib.ptr(f), n, w, h, int(rot90), _lib.ptr(t), Cn, self.logit_scale, _lib.ptr(logits), _lib.ptr(emb)))
         return (logits, emb) if return_embeds else logits
 
     def preprocess(self, frames_u8, rot90: bool = True) -> np.ndarray:
@@ -342,15 +334,14 @@ class ClipScorer:
         n, h, w, _ = f.shape
         S = self.cfg["image_size"]
         pv = np.empty((n, 3, S, S), np.float32)
-        self.ctx.check(self.ctx.lib.d2r_clip_preprocess(self.ctx.h, self.h, _lib.ptr(f), C.c_uint32(n), C.c_uint32(w),
-                                                        C.c_uint32(h), C.c_int(int(rot90)), _lib.ptr(pv)))
+        self.ctx.check(self.ctx.lib.d2r_clip_preprocess(self.ctx.h, self.h, _lib.ptr(f), n, w, h, int(rot90), _lib.ptr(pv)))
         return pv
 
     def embed_pixels(self, pixel_values) -> np.ndarray:
         pv = np.ascontiguousarray(pixel_values, np.float32)
         n = pv.shape[0]
         emb = np.empty((n, self.cfg["proj"]), np.float32)
-        self.ctx.check(self.ctx.lib.d2r_clip_embed_pixels(self.ctx.h, self.h, _lib.ptr(pv), C.c_uint32(n), _lib.ptr(emb)))
+        self.ctx.check(self.ctx.lib.d2r_clip_embed_pixels(self.ctx.h, self.h, _lib.ptr(pv), n, _lib.ptr(emb)))
         return emb
 
 
@@ -364,7 +355,7 @@ class TextEncoder:
         desc = _lib.TextDesc(cfg["vocab"], cfg["ctx"], cfg["text_hidden"], cfg["text_layers"], cfg["text_heads"],
                              cfg["text_mlp"], cfg["proj"])
         h = C.c_void_p()
-        ctx.check(ctx.lib.d2r_text_create(ctx.h, C.byref(desc), _lib.ptr(blob), C.c_size_t(blob.size), C.byref(h)))
+        ctx.check(ctx.lib.d2r_text_create(ctx.h, C.byref(desc), _lib.ptr(blob), blob.size, C.byref(h)))
         self.h = h
 
     def close(self):
@@ -382,8 +373,7 @@ class TextEncoder:
         ids = np.ascontiguousarray(input_ids, np.int32)
         Cn, T = ids.shape
         out = np.empty((Cn, self.cfg["proj"]), np.float32)
-        self.ctx.check(self.ctx.lib.d2r_text_encode(self.ctx.h, self.h, _lib.ptr(ids), C.c_uint32(Cn), C.c_uint32(T),
-                                                    _lib.ptr(out)))
+        self.ctx.check(self.ctx.lib.d2r_text_encode(self.ctx.h, self.h, _lib.ptr(ids), Cn, T, _lib.ptr(out)))
         return out
 
 
@@ -407,8 +397,7 @@ def render_score_host(ctx: Context, fg: Testbed, scorer: ClipScorer, view: View,
         sink = _lib.FrameSink(os.fsencode(png_dir), png_first_index, png_threads, png_level)
     v = _lib.view_c(view)
     ctx.check(ctx.lib.d2r_render_score_host(ctx.h, fg.h, scorer.h, C.byref(v), _lib.ptr(a), _lib.ptr(c), _lib.ptr(p),
-                                            C.c_uint32(K), _lib.ptr(t), C.c_uint32(Cn), C.c_float(scorer.logit_scale),
-                                            _lib.ptr(logits), _lib.ptr(frames), C.byref(sink) if sink is not None else None))
+                                            K, _lib.ptr(t), Cn, scorer.logit_scale, _lib.ptr(logits), _lib.ptr(frames), C.byref(sink) if sink is not None else None))
     return (logits, frames) if return_frames else logits
 
 
@@ -420,7 +409,5 @@ def render_score_device(ctx: Context, fg: Testbed, scorer: ClipScorer, view: Vie
     c = np.ascontiguousarray(np.asarray(cam_pose, np.float64).reshape(16), np.float32)
     t = np.ascontiguousarray(text_embeds, np.float32)
     v = _lib.view_c(view)
-    ctx.check(ctx.lib.d2r_render_score(ctx.h, fg.h, scorer.h, C.byref(v), _lib.ptr(a), _lib.ptr(c),
-                                       C.c_void_p(obj_poses_dev_ptr), C.c_uint32(K), _lib.ptr(t),
-                                       C.c_uint32(t.shape[0]), C.c_float(scorer.logit_scale),
-                                       C.c_void_p(logits_dev_ptr), _lib.ptr(frames_out)))
+    ctx.check(ctx.lib.d2r_render_score(ctx.h, fg.h, scorer.h, C.byref(v), _lib.ptr(a), _lib.ptr(c), obj_poses_dev_ptr, K,
+                                       _lib.ptr(t), t.shape[0], scorer.logit_scale, logits_dev_ptr, _lib.ptr(frames_out)))

@@ -396,8 +396,7 @@ class PointCloudRenderer:
         if hit is not None and hit[0] is pcd:
             return hit[1]
         h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.d2r_pcd_create(self.ctx.h, _lib.ptr(pcd.xyz), _lib.ptr(pcd.rgb), C.c_uint32(len(pcd)),
-                                                   C.byref(h)))
+        self.ctx.check(self.ctx.lib.d2r_pcd_create(self.ctx.h, _lib.ptr(pcd.xyz), _lib.ptr(pcd.rgb), len(pcd), C.byref(h)))
         self._uploads[id(pcd)] = (pcd, h)
         return h
 
@@ -417,7 +416,7 @@ class PointCloudRenderer:
         K = poses.shape[0]
         frames = np.empty((K, self.height, self.width, 3), np.uint8)
         self.ctx.check(self.ctx.lib.d2r_pcd_render(self.ctx.h, bg, mv, C.byref(self.view), _lib.ptr(cam), _lib.ptr(now),
-                                                   _lib.ptr(poses), C.c_uint32(K), _lib.ptr(frames)))
+                                                   _lib.ptr(poses), K, _lib.ptr(frames)))
         return list(frames)
 
     def render_score(self, render_pose, pose_batch, task_model, scorer, text_embeds, return_frames: bool = False):
@@ -430,8 +429,8 @@ class PointCloudRenderer:
         frames = np.empty((K, self.height, self.width, 3), np.uint8) if return_frames else None
         if K:
             self.ctx.check(self.ctx.lib.d2r_pcd_render_score_host(
-                self.ctx.h, bg, mv, scorer.h, C.byref(self.view), _lib.ptr(cam), _lib.ptr(now), _lib.ptr(poses), C.c_uint32(K),
-                _lib.ptr(t), C.c_uint32(t.shape[0]), C.c_float(scorer.logit_scale), _lib.ptr(logits), _lib.ptr(frames)))
+                self.ctx.h, bg, mv, scorer.h, C.byref(self.view), _lib.ptr(cam), _lib.ptr(now), _lib.ptr(poses), K,
+                _lib.ptr(t), t.shape[0], scorer.logit_scale, _lib.ptr(logits), _lib.ptr(frames)))
         return (logits, frames) if return_frames else logits
 
     def close(self):

@@ -136,8 +136,8 @@ class PhysicsShapes:
         mv, moff = _pack(movable_hulls)
         sv, soff = _pack(static_hulls)
         h = C.c_void_p()
-        ctx.check(ctx.lib.d2r_phys_create(ctx.h, _lib.ptr(mv), _lib.ptr(moff), C.c_uint32(len(moff) - 1),
-                                          _lib.ptr(sv) if len(sv) else None, _lib.ptr(soff), C.c_uint32(len(soff) - 1), C.byref(h)))
+        ctx.check(ctx.lib.d2r_phys_create(ctx.h, _lib.ptr(mv), _lib.ptr(moff), len(moff) - 1,
+                                          _lib.ptr(sv) if len(sv) else None, _lib.ptr(soff), len(soff) - 1, C.byref(h)))
         self.h = h
 
     def close(self):
@@ -156,12 +156,8 @@ class PhysicsShapes:
         poses = np.ascontiguousarray(np.asarray(pose_batch, np.float64).reshape(-1, 16), np.float32)
         valid = np.ascontiguousarray(np.asarray(valid_so_far).astype(np.uint8).reshape(-1))
         assert valid.shape[0] == poses.shape[0]
-        prm = _lib.PhysParams((C.c_uint32 * 6)(*[int(x) for x in sample_res]),
-                              (C.c_float * 16)(*np.asarray(init_pose, np.float64).reshape(16)),
-                              float(table_z), float(unsup_thresh), (C.c_float * 3)(*[float(x) for x in GRAVITY_DIRECTION]),
-                              float(perturb), int(bool(stability_check)), int(bool(disallow_regrasp)), float(margin))
-        self.ctx.check(self.ctx.lib.d2r_phys_check(self.ctx.h, self.h, C.byref(prm), _lib.ptr(poses),
-                                                   C.c_uint32(poses.shape[0]), _lib.ptr(valid)))
+        prm = _phys_params(sample_res, init_pose, table_z, unsup_thresh, perturb, stability_check, disallow_regrasp, margin)
+        self.ctx.check(self.ctx.lib.d2r_phys_check(self.ctx.h, self.h, C.byref(prm), _lib.ptr(poses), poses.shape[0], _lib.ptr(valid)))
         return valid.astype(bool)
 
 
@@ -210,8 +206,8 @@ class SdfPhysicsShapes:
             raise ValueError(f"touch words of shape {w.shape} do not fit the grid {nx} x {ny} x {nz}")
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         h = C.c_void_p()
-        ctx.check(ctx.lib.d2r_sdfphys_create(ctx.h, _lib.ptr(b0), _lib.ptr(nv), C.c_float(voxel), _lib.ptr(w), C.c_uint32(w.shape[0]),
-                                             _lib.ptr(pts), C.c_uint32(pts.shape[0]), C.byref(h)))
+        ctx.check(ctx.lib.d2r_sdfphys_create(ctx.h, _lib.ptr(b0), _lib.ptr(nv), voxel, _lib.ptr(w), w.shape[0],
+                                             _lib.ptr(pts), pts.shape[0], C.byref(h)))
         self.h = h
         self.n_points = pts.shape[0]
 
@@ -249,8 +245,7 @@ class SdfPhysicsShapes:
         valid = np.ascontiguousarray(np.asarray(valid_so_far).astype(np.uint8).reshape(-1))
         assert valid.shape[0] == poses.shape[0]
         prm = _phys_params(sample_res, init_pose, table_z, unsup_thresh, perturb, stability_check, disallow_regrasp, 0.0)
-        self.ctx.check(self.ctx.lib.d2r_sdfphys_check(self.ctx.h, self.h, C.byref(prm), _lib.ptr(poses),
-                                                      C.c_uint32(poses.shape[0]), _lib.ptr(valid)))
+        self.ctx.check(self.ctx.lib.d2r_sdfphys_check(self.ctx.h, self.h, C.byref(prm), _lib.ptr(poses), poses.shape[0], _lib.ptr(valid)))
         return valid.astype(bool)
 
     def timing(self):
@@ -348,7 +343,7 @@ class TsdfVolume:
         self.trunc = np.float32(TSDF_TRUNC_MULTIPLIER) * self.voxel if trunc is None else np.float32(trunc)
         b = np.ascontiguousarray(np.asarray(_np(bounds), np.float64).reshape(6), np.float32)
         h = C.c_void_p()
-        ctx.check(ctx.lib.d2r_tsdf_create(ctx.h, _lib.ptr(b), C.c_float(self.voxel), C.c_float(self.trunc), C.byref(h)))
+        ctx.check(ctx.lib.d2r_tsdf_create(ctx.h, _lib.ptr(b), self.voxel, self.trunc, C.byref(h)))
         self.h = h
 
     def close(self):
@@ -368,8 +363,8 @@ class TsdfVolume:
         assert d.ndim == 2 and m.shape == d.shape
         K = np.ascontiguousarray(np.asarray(_np(intrinsics), np.float64).reshape(9), np.float32)
         T = np.ascontiguousarray(np.asarray(_np(cam_pose), np.float64).reshape(16), np.float32)
-        self.ctx.check(self.ctx.lib.d2r_tsdf_integrate(self.h, _lib.ptr(d), _lib.ptr(m), C.c_uint32(d.shape[1]), C.c_uint32(d.shape[0]),
-                                                       _lib.ptr(K), _lib.ptr(T), C.c_uint32(int(erode_k))))
+        self.ctx.check(self.ctx.lib.d2r_tsdf_integrate(self.h, _lib.ptr(d), _lib.ptr(m), d.shape[1], d.shape[0],
+                                                       _lib.ptr(K), _lib.ptr(T), int(erode_k)))
 
     def read_voxels(self):
         """-> (block coordinates int32 [n,3] (x, y, z), tsdf float32 [n,16,16,16] indexed [z][y][x], weight likewise), the
@@ -388,7 +383,7 @@ class TsdfVolume:
         [nt] (False: in a cluster below cluster_keep of the largest), centre float64 [3]."""
         c = None if crop is None else np.ascontiguousarray(np.asarray(_np(crop), np.float64).reshape(6), np.float32)
         nv, nt = C.c_uint32(0), C.c_uint32(0)
-        args = (self.h, C.c_float(weight_threshold), _lib.ptr(c), C.c_double(cluster_keep), C.byref(nv), C.byref(nt))
+        args = (self.h, weight_threshold, _lib.ptr(c), cluster_keep, C.byref(nv), C.byref(nt))
         self.ctx.check(self.ctx.lib.d2r_tsdf_extract(*args, None, None, None, None, None))
         v = np.zeros((nv.value, 3), np.float32)
         t = np.zeros((nt.value, 3), np.uint32)
@@ -411,15 +406,15 @@ class TsdfVolume:
         surface or behind it."""
         nx, ny, nz = (int(v) for v in self.grid()[1])
         words = np.zeros((nz, ny, (nx + 31) // 32), np.uint32)
-        self.ctx.check(self.ctx.lib.d2r_tsdf_touch_bits(self.h, C.c_float(weight_threshold), C.c_float(contact), _lib.ptr(words)))
+        self.ctx.check(self.ctx.lib.d2r_tsdf_touch_bits(self.h, weight_threshold, contact, _lib.ptr(words)))
         return words
 
     def solid_points(self, weight_threshold: float = TSDF_WEIGHT_THRESHOLD) -> np.ndarray:
         """-> float32 [n, 3]: the centres of the observed solid voxels (weight >= threshold, tsdf <= 0) in (z, y, x) order."""
         n = C.c_uint32(0)
-        self.ctx.check(self.ctx.lib.d2r_tsdf_solid_points(self.h, C.c_float(weight_threshold), C.byref(n), None))
+        self.ctx.check(self.ctx.lib.d2r_tsdf_solid_points(self.h, weight_threshold, C.byref(n), None))
         xyz = np.zeros((n.value, 3), np.float32)
-        self.ctx.check(self.ctx.lib.d2r_tsdf_solid_points(self.h, C.c_float(weight_threshold), C.byref(n), _lib.ptr(xyz)))
+        self.ctx.check(self.ctx.lib.d2r_tsdf_solid_points(self.h, weight_threshold, C.byref(n), _lib.ptr(xyz)))
         return xyz
 
 

@@ -26,6 +26,110 @@ def test_header_symbols_are_exported():
     assert lib.d2r_abi_version() == _lib.ABI_VERSION == int(re.search(r"#define D2R_ABI_VERSION (\d+)", open(os.path.join(REPO, "include", "d2r.h")).read()).group(1))
 
 
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+# the ctypes.Structure mirrors of _lib and the typedef each one restates
+_MIRRORS = {"NerfDesc": "d2r_nerf_desc", "ViewC": "d2r_view", "ClipDesc": "d2r_clip_desc", "TextDesc": "d2r_text_desc",
+            "PhysParams": "d2r_phys_params", "IngpView": "d2r_ingp_view", "IngpInfo": "d2r_ingp_info", "PcdView": "d2r_pcd_view",
+            "FrameSink": "d2r_frame_sink", "RenderStats": "d2r_render_stats", "Timing": "d2r_timing"}
+
+
+def _header_without_comments():
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "d2r.h")).read(), flags=re.S)
+
+
+def _ctype(c_type, where):
+    """The binding's type for a C type, by the rule written above _lib.PROTOTYPES: scalars exactly, `const char *` as c_char_p,
+    every other pointer as c_void_p, void as None."""
+    t = " ".join(c_type.replace("*", " * ").split())
+    if "*" in t:
+        return ctypes.c_char_p if t == "const char *" else ctypes.c_void_p
+    t = t[len("const "):] if t.startswith("const ") else t
+    assert t == "void" or t in _SCALARS, f"{where}: the rule has no ctypes type for {c_type.strip()!r}"
+    return _SCALARS.get(t)
+
+
+def _name(t):
+    return getattr(t, "__name__", repr(t))
+
+
+def test_binding_prototypes_match_the_header():
+    """_lib.PROTOTYPES, which load() declares on the library, says what include/d2r.h says: every D2R_API prototype's return type and
+    parameter types in order, mapped by the table's rule.  A function without a table line, or a line that disagrees, fails here."""
+    h = _header_without_comments()
+    protos = re.findall(r"\bD2R_API\s+([^;()]+?)\b(d2r_\w+)\s*\(([^()]*)\)\s*;", h)
+    assert len(protos) == len(_declared_symbols()) == len(re.findall(r"\bD2R_API\b", h)) - 1         # - 1: the #define; nothing skipped
+    assert sorted(_lib.PROTOTYPES) == sorted(name for _, name, _ in protos)
+    lib = _lib.load()
+    for ret, name, params in protos:
+        restype, argtypes = _lib.PROTOTYPES[name]
+        want_ret = _ctype(ret, name)
+        assert restype is want_ret, f"{name}: returns {_name(want_ret)} by the header ({ret.strip()}), {_name(restype)} in the table"
+        want = []
+        for i, p in enumerate([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"\s*(.+?)(\w+)\s*", p, re.S)           # the type, then the parameter's name
+            assert m and "[" not in p, f"{name}: cannot parse parameter {i}, {p.strip()!r}"
+            want.append((_ctype(m.group(1), f"{name}, parameter {i}"), p.strip()))
+        assert len(argtypes) == len(want), f"{name}: {len(want)} parameters in the header, {len(argtypes)} in the table"
+        for i, (got, (w, text)) in enumerate(zip(argtypes, want)):
+            assert got is w, f"{name}: parameter {i} is {_name(w)} by the header ({text}), {_name(got)} in the table"
+        fn = getattr(lib, name)
+        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), f"{name}: load() did not declare the table's line"
+
+
+def _header_structs():
+    """typedef name -> [(field, ctypes type)] of every `typedef struct { ... } d2r_x;`, parsed from the header's text."""
+    structs = {}
+    for body, name in re.findall(r"\btypedef\s+struct\s*\{([^{}]*)\}\s*(d2r_\w+)\s*;", _header_without_comments()):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            base, declarators = re.fullmatch(r"((?:const\s+)?\w+)\b(.*)", decl, re.S).groups()
+            for d in declarators.split(","):
+                m = re.fullmatch(r"\s*(\**)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", d)          # stars, name, array length
+                assert m, f"{name}: cannot parse the declaration {decl!r}"
+                t = _ctype(base + " " + m.group(1), f"{name}.{m.group(2)}")
+                fields.append((m.group(2), t * int(m.group(3)) if m.group(3) else t))
+        structs[name] = fields
+    return structs
+
+
+def test_struct_mirrors_match_the_header(tmp_path):
+    """Every ctypes.Structure of _lib restates its typedef of include/d2r.h: the same fields in the same order with the types of the
+    table's rule (array lengths included), and the size and the field offsets a C compiler gives the header's struct."""
+    import shutil
+    import subprocess
+    structs = _header_structs()
+    mirrors = {n for n, v in vars(_lib).items() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert mirrors == set(_MIRRORS) and sorted(structs) == sorted(_MIRRORS.values())
+    for py_name, c_name in _MIRRORS.items():
+        got, want = getattr(_lib, py_name)._fields_, structs[c_name]
+        assert [f for f, _ in got] == [f for f, _ in want], f"{py_name}: fields differ from {c_name}'s in name or order"
+        for (field, t), (_, w) in zip(got, want):
+            assert t is w, f"{py_name}.{field} is {_name(w)} by the header, {_name(t)} in the mirror"
+    gcc = shutil.which("gcc")
+    if not gcc:
+        pytest.skip("no gcc")
+    lines = []
+    for c_name, fields in structs.items():
+        lines.append(f'printf("{c_name} %zu\\n", sizeof({c_name}));')
+        lines += [f'printf("{c_name}.{f} %zu\\n", offsetof({c_name}, {f}));' for f, _ in fields]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "d2r.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(REPO, "include"), str(src), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    compiled = {k: int(v) for k, v in (line.split() for line in r.stdout.splitlines())}
+    for py_name, c_name in _MIRRORS.items():
+        cls = getattr(_lib, py_name)
+        assert ctypes.sizeof(cls) == compiled[c_name], f"sizeof({c_name}) is {compiled[c_name]}, the mirror {py_name} has {ctypes.sizeof(cls)}"
+        for field, _ in cls._fields_:
+            assert getattr(cls, field).offset == compiled[f"{c_name}.{field}"], \
+                f"offsetof({c_name}, {field}) is {compiled[f'{c_name}.{field}']}, {py_name}.{field}.offset is {getattr(cls, field).offset}"
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():
@@ -272,7 +376,6 @@ def test_host_only_entries_return_error_codes(tmp_path):
     assert lib.d2r_png_read_batch(os.fsencode(str(tmp_path)), None, 7, 1, 6, 4, _lib.ptr(img), 0) == -1 and "cb_rgb_0007.png" in err()
     w, h = C.c_uint32(), C.c_uint32()
     assert lib.d2r_png_size(os.fsencode(str(tmp_path / "missing.png")), C.byref(w), C.byref(h)) == -1
-    lib.d2r_savetxt.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int]
     a = np.arange(6, dtype=np.float64)
     assert lib.d2r_savetxt(None, _lib.ptr(a), 2, 3, 0) == -1
     assert lib.d2r_savetxt(os.fsencode(str(tmp_path / "t.txt")), None, 2, 3, 0) == -1
@@ -281,7 +384,6 @@ def test_host_only_entries_return_error_codes(tmp_path):
     assert lib.d2r_savetxt(os.fsencode(str(tmp_path / "empty.txt")), None, 0, 3, 0) == 0 and open(tmp_path / "empty.txt").read() == ""
     assert lib.d2r_savetxt(os.fsencode(str(tmp_path / "t.txt")), _lib.ptr(a), 2, 3, 1) == 0
     np.testing.assert_array_equal(np.loadtxt(tmp_path / "t.txt"), a.reshape(2, 3))
-    lib.d2r_ingp_validate.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
     assert lib.d2r_ingp_validate(None, 100, None) == -1 and lib.d2r_ingp_validate(b"abc", 3, None) == -1
     assert lib.d2r_ingp_validate(bytes(range(64)), 64, None) == -1 and "snapshot" in err()
     with pytest.raises(ValueError):
