@@ -57,29 +57,64 @@ def matrices(cam_pose, obj_pose_now, obj_poses):
     return Ci[:3].astype(np.float32), M[:, :3].astype(np.float32)
 
 
-def project(M, xyz, view: PcdView):
-    """-> (z fp32 [N], j0 int64 [N], i0 int64 [N], ok bool [N])."""
+# One departure from the rule at a time, for tests that prove their cases can tell the rule from its near misses
+# (tests/test_pcd_edges_host.py).  `wrong=None`, the default everywhere, is the rule.
+WRONG_RULES = (
+    "floor_plus_one",     # sprite starts at floor(u - ps / 2) + 1 instead of ceil(u - ps / 2)
+    "keep_z_eq_near",     # a point with z' == near is kept
+    "ties_high",          # equal depths go to the higher global index
+    "z24",                # keys compare z' truncated to the upper 24 bits of its pattern
+    "ge_220",             # all three channels >= 220 -> black
+    "white_stays",        # a pixel no point reaches stays white
+    "cull_ge_minus_ps",   # kept when a >= -ps (and b >= -ps)
+    "cull_le_size",       # kept when a <= W (and b <= H)
+)
+
+
+def project_uv(M, xyz, view: PcdView):
+    """-> (u, v, z) fp32 [N]: the image coordinates and the camera-space depth before any cull (inf / NaN where they overflow)."""
     M = np.asarray(M, np.float32)
     p = np.asarray(xyz, np.float32).reshape(-1, 3)
-    x, y, z = (((M[r, 0] * p[:, 0] + M[r, 1] * p[:, 1]) + M[r, 2] * p[:, 2]) + M[r, 3] for r in range(3))
-    f = np.float32
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        x, y, z = (((M[r, 0] * p[:, 0] + M[r, 1] * p[:, 1]) + M[r, 2] * p[:, 2]) + M[r, 3] for r in range(3))
+        f = np.float32
         u = (f(view.fx) * x) / z + f(view.cx)
         v = (f(view.fy) * y) / z + f(view.cy)
+    return u, v, z
+
+
+def project(M, xyz, view: PcdView, wrong=None):
+    """-> (z fp32 [N], j0 int64 [N], i0 int64 [N], ok bool [N])."""
+    u, v, z = project_uv(M, xyz, view)
+    f = np.float32
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         half = f(view.point_size) * f(0.5)
-        a, b = np.ceil(u - half), np.ceil(v - half)
+        if wrong == "floor_plus_one":
+            a, b = np.floor(u - half) + f(1), np.floor(v - half) + f(1)
+        else:
+            a, b = np.ceil(u - half), np.ceil(v - half)
         ps = f(view.point_size)
-        ok = (z > f(view.near)) & (a > -ps) & (a < f(view.width)) & (b > -ps) & (b < f(view.height))
+        W, H = f(view.width), f(view.height)
+        front = z >= f(view.near) if wrong == "keep_z_eq_near" else z > f(view.near)
+        lo = (a >= -ps) & (b >= -ps) if wrong == "cull_ge_minus_ps" else (a > -ps) & (b > -ps)
+        hi = (a <= W) & (b <= H) if wrong == "cull_le_size" else (a < W) & (b < H)
+        ok = front & lo & hi
     j0 = np.where(ok, a, 0).astype(np.int64)
     i0 = np.where(ok, b, 0).astype(np.int64)
     return z, j0, i0, ok
 
 
-def splat(keys, M, xyz, first_index, view: PcdView):
+def splat(keys, M, xyz, first_index, view: PcdView, wrong=None):
     """keys [H*W] uint64 <- minimum with the cloud's sprites (in place)."""
-    z, j0, i0, ok = project(M, xyz, view)
+    z, j0, i0, ok = project(M, xyz, view, wrong)
     idx = np.nonzero(ok)[0]
-    key = (z[idx].view(np.uint32).astype(np.uint64) << np.uint64(32)) | (idx + first_index).astype(np.uint64)
+    zbits = z[idx].view(np.uint32).astype(np.uint64)
+    if wrong == "z24":
+        zbits &= np.uint64(0xFFFFFF00)
+    low = (idx + first_index).astype(np.uint64)
+    if wrong == "ties_high":
+        low = np.uint64(0xFFFFFFFF) - low            # resolve() undoes it
+    key = (zbits << np.uint64(32)) | low
     ps = int(view.point_size)
     for dr in range(ps):
         for dc in range(ps):
@@ -89,20 +124,27 @@ def splat(keys, M, xyz, first_index, view: PcdView):
     return keys
 
 
-def resolve(keys, colours, view: PcdView):
+def resolve(keys, colours, view: PcdView, wrong=None):
     """keys [H*W] -> uint8 [H,W,3] through the colour table (background then movable)."""
     out = np.full((keys.shape[0], 3), 255, np.uint8)
     hit = keys != EMPTY
-    out[hit] = colours[(keys[hit] & np.uint64(0xFFFFFFFF)).astype(np.int64)]
-    out[np.all(out > 220, axis=-1)] = 0
+    low = keys[hit] & np.uint64(0xFFFFFFFF)
+    if wrong == "ties_high":
+        low = np.uint64(0xFFFFFFFF) - low
+    out[hit] = colours[low.astype(np.int64)]
+    black = np.all(out >= 220, axis=-1) if wrong == "ge_220" else np.all(out > 220, axis=-1)
+    if wrong == "white_stays":
+        black &= hit
+    out[black] = 0
     return out.reshape(view.height, view.width, 3)
 
 
-def render(bg_xyz, bg_rgb, mv_xyz, mv_rgb, view: PcdView, cam_pose, obj_pose_now, obj_poses):
-    """-> uint8 [K,H,W,3]: what d2r_pcd_render must return, bit for bit."""
+def render(bg_xyz, bg_rgb, mv_xyz, mv_rgb, view: PcdView, cam_pose, obj_pose_now, obj_poses, wrong=None):
+    """-> uint8 [K,H,W,3]: what d2r_pcd_render must return, bit for bit (with `wrong`: one of WRONG_RULES in its place)."""
+    assert wrong is None or wrong in WRONG_RULES, wrong
     Mb, Mk = matrices(cam_pose, obj_pose_now, obj_poses)
     nb = np.asarray(bg_xyz).reshape(-1, 3).shape[0]
     colours = np.concatenate([np.asarray(bg_rgb, np.uint8).reshape(-1, 3), np.asarray(mv_rgb, np.uint8).reshape(-1, 3)], 0)
-    bg_keys = splat(np.full(view.width * view.height, EMPTY, np.uint64), Mb, bg_xyz, 0, view)
-    return np.stack([resolve(splat(bg_keys.copy(), M, mv_xyz, nb, view), colours, view) for M in Mk]) if len(Mk) else \
+    bg_keys = splat(np.full(view.width * view.height, EMPTY, np.uint64), Mb, bg_xyz, 0, view, wrong)
+    return np.stack([resolve(splat(bg_keys.copy(), M, mv_xyz, nb, view, wrong), colours, view, wrong) for M in Mk]) if len(Mk) else \
         np.zeros((0, view.height, view.width, 3), np.uint8)
