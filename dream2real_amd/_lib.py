@@ -79,6 +79,8 @@ PROTOTYPES = {
     "d2r_tsdf_read_voxels": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr)),
     "d2r_tsdf_extract": (_int, (_ptr, _f32, _ptr, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
     "d2r_obj_write": (_int, (_str, _ptr, _u32, _ptr, _u32, _ptr)),
+    "d2r_obj_read": (_int, (_str, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_mesh_render": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _u32, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr)),
     "d2r_tsdf_grid": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr)),
     "d2r_tsdf_touch_bits": (_int, (_ptr, _f32, _f32, _ptr)),
     "d2r_tsdf_solid_points": (_int, (_ptr, _f32, _ptr, _ptr)),
@@ -311,6 +313,42 @@ def obj_write(path: str, vertices, triangles, keep=None):
     k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
     assert k is None or k.shape[0] == t.shape[0]
     check(load().d2r_obj_write(os.fsencode(path), ptr(v), v.shape[0], ptr(t), t.shape[0], ptr(k)))
+
+
+def obj_read(path: str):
+    """d2r_obj_read: a Wavefront .obj -> (vertices float32 [nv,3], triangles uint32 [nt,3]); faces of more than three corners become
+    fans, groups are concatenated.  Host only."""
+    lib = load()
+    nv, nt = C.c_uint32(0), C.c_uint32(0)
+    check(lib.d2r_obj_read(os.fsencode(path), C.byref(nv), C.byref(nt), None, None))
+    v, t = np.empty((nv.value, 3), np.float32), np.empty((nt.value, 3), np.uint32)
+    check(lib.d2r_obj_read(os.fsencode(path), C.byref(nv), C.byref(nt), ptr(v), ptr(t)))
+    return v, t
+
+
+def mesh_render(ctx, view: PcdView, cam_pose, verts, tris, tri_item, item_mats, item_rgb, cube_centres=None, cube_half=None,
+                cube_scores=None, background=(255, 255, 255), return_ids: bool = False):
+    """d2r_mesh_render: a triangle soup of coloured items and score cubes -> uint8 [h,w,3] (and the int32
+    [h,w] ids image: the triangle, -1 - cube, or INT32_MIN)."""
+    f32 = lambda a, shape: np.ascontiguousarray(a, np.float32).reshape(shape)
+    cam = f32(cam_pose, 16)
+    v = f32(verts if verts is not None else [], (-1, 3))
+    t = np.ascontiguousarray(tris if tris is not None else [], np.uint32).reshape(-1, 3)
+    it = np.ascontiguousarray(tri_item if tri_item is not None else [], np.uint32).reshape(-1)
+    mats = f32(item_mats if item_mats is not None else [], (-1, 16))
+    cols = np.ascontiguousarray(item_rgb if item_rgb is not None else [], np.uint8).reshape(-1, 3)
+    cc = f32(cube_centres if cube_centres is not None else [], (-1, 3))
+    ch = f32(cube_half if cube_half is not None else [], -1)
+    cs = np.ascontiguousarray(cube_scores if cube_scores is not None else [], np.uint16).reshape(-1)
+    if it.shape[0] != t.shape[0] or cols.shape[0] != mats.shape[0] or not (cc.shape[0] == ch.shape[0] == cs.shape[0]):
+        raise ValueError("mesh_render: tri_item per triangle, one colour per item matrix, one half-width and one score per cube")
+    bg = np.ascontiguousarray(background, np.uint8).reshape(3)
+    rgb = np.empty((view.height, view.width, 3), np.uint8)
+    ids = np.empty((view.height, view.width), np.int32) if return_ids else None
+    some = lambda a: ptr(a) if a.size else None
+    check(load().d2r_mesh_render(_h(ctx), C.byref(view), ptr(cam), some(v), v.shape[0], some(t), some(it), t.shape[0], some(mats), some(cols),
+                                 mats.shape[0], some(cc), some(ch), some(cs), cs.shape[0], ptr(bg), ptr(rgb), ptr(ids)), _h(ctx))
+    return (rgb, ids) if return_ids else rgb
 
 
 def _h(ctx):

@@ -128,6 +128,7 @@ struct d2r_ctx {
     // background of the current view
     Buf bg_rgba, bg_depth, bg_u8;
     Buf pcd_mats, pcd_bg_keys, pcd_bg_frame, pcd_cols;   // pcd.hip: candidate matrices, background key buffer and colour frame, colour table of the current call
+    Buf mv_in, mv_recs, mv_queue, mv_shade, mv_keys, mv_out;   // meshvis.hip: uploaded inputs, triangle records, the large-triangle queue, shade bytes, mesh + cube key buffers, rgb + ids of the current call
     Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots, result frames, union-find parents + component statistics of a pass
     hipEvent_t mask_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... upload / kernels / download boundaries of the last batch call (d2r_masks_get_timing)
     bool mask_timed = false;
@@ -235,6 +236,7 @@ struct PerDeviceOnce {
 };
 
 int d2r_reserve(d2r_ctx *ctx, d2r_ctx::Buf &b, size_t bytes);
+int d2r_pcd_check_view(d2r_ctx *ctx, const d2r_pcd_view *view);      // pcd.hip: the limits d2r_pcd_render holds a view to (meshvis.hip shares them)
 
 // phys.hip: the host side the two physics pre-filters (hulls + GJK in phys.hip, points against the TSDF field in sdfphys.hip) share
 int d2r_phys_orientations(d2r_ctx *, const d2r_phys_params *, uint32_t N, uint64_t *oris_out);      // checks N against sample_res -> orientations per position

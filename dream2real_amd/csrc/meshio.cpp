@@ -3,6 +3,7 @@
 // small ones, the centre of the vertex array, and mesh_concave_{id}.obj.  None of it is hot: one pass each over a mesh of
 // some 10^5 triangles.
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -102,5 +103,82 @@ extern "C" int d2r_obj_write(const char *path, const float *vertices, uint32_t n
     }
     const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
     if (fclose(f) != 0 || !ok) return d2r_fail(nullptr, D2R_ERR_INVALID, std::string("short write to ") + path);
+    return D2R_OK;
+}
+
+// `v` and `f` lines of a Wavefront .obj; see include/d2r.h.  A number is read as fp64 (strtod) and rounded to fp32.
+extern "C" int d2r_obj_read(const char *path, uint32_t *n_vertices, uint32_t *n_triangles, float *vertices, uint32_t *triangles)
+{
+    if (!path || !n_vertices || !n_triangles) return d2r_fail(nullptr, D2R_ERR_INVALID, "null argument");
+    FILE *f = fopen(path, "rb");
+    if (!f) return d2r_fail(nullptr, D2R_ERR_INVALID, std::string("cannot open ") + path + " for reading");
+    std::string s;
+    char chunk[1 << 16];
+    size_t got;
+    while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) s.append(chunk, got);
+    const bool read_ok = !ferror(f);
+    fclose(f);
+    if (!read_ok) return d2r_fail(nullptr, D2R_ERR_INVALID, std::string("cannot read ") + path);
+    const uint64_t cap_v = vertices ? *n_vertices : 0, cap_t = triangles ? *n_triangles : 0;
+    uint64_t nv = 0, nt = 0, line_no = 0;
+    auto bad = [&](const char *what) {
+        return d2r_fail(nullptr, D2R_ERR_INVALID, std::string(path) + ", line " + std::to_string(line_no) + ": " + what);
+    };
+    const char *p = s.c_str(), *end = p + s.size();          // (c_str: NUL-terminated, so strtod and strtol stop at the end)
+    while (p < end) {
+        ++line_no;
+        const char *eol = (const char *)memchr(p, '\n', (size_t)(end - p));
+        if (!eol) eol = end;
+        const char *q = p;
+        while (q < eol && (*q == ' ' || *q == '\t')) ++q;
+        if (q + 1 < eol && q[0] == 'v' && (q[1] == ' ' || q[1] == '\t')) {
+            q += 2;
+            double xyz[3];
+            for (int a = 0; a < 3; ++a) {
+                char *e;
+                xyz[a] = strtod(q, &e);
+                if (e == q || e > eol) return bad("a vertex needs three numbers");
+                q = e;
+            }
+            if (nv >= 0xffffffffull) return bad("too many vertices");
+            if (vertices) {
+                if (nv >= cap_v) return bad("more vertices than the buffer holds");
+                for (int a = 0; a < 3; ++a) vertices[3 * nv + a] = (float)xyz[a];
+            }
+            ++nv;
+        } else if (q + 1 < eol && q[0] == 'f' && (q[1] == ' ' || q[1] == '\t')) {
+            q += 2;
+            uint32_t first = 0, prev = 0;
+            int corners = 0;
+            for (;;) {
+                while (q < eol && (*q == ' ' || *q == '\t' || *q == '\r')) ++q;
+                if (q >= eol) break;
+                char *e;
+                const long long idx = strtoll(q, &e, 10);
+                if (e == q || e > eol) return bad("a face corner is not an index");
+                q = e;
+                while (q < eol && *q != ' ' && *q != '\t' && *q != '\r') ++q;      // the /vt/vn parts
+                const long long v = idx > 0 ? idx - 1 : (long long)nv + idx;
+                if (idx == 0 || v < 0 || v >= (long long)nv) return bad("a face index is out of range");
+                if (corners == 0) first = (uint32_t)v;
+                if (corners >= 2) {
+                    if (nt >= 0xffffffffull) return bad("too many triangles");
+                    if (triangles) {
+                        if (nt >= cap_t) return bad("more triangles than the buffer holds");
+                        triangles[3 * nt] = first;
+                        triangles[3 * nt + 1] = prev;
+                        triangles[3 * nt + 2] = (uint32_t)v;
+                    }
+                    ++nt;
+                }
+                prev = (uint32_t)v;
+                ++corners;
+            }
+            if (corners < 3) return bad("a face needs three corners");
+        }
+        p = eol + 1;
+    }
+    *n_vertices = (uint32_t)nv;
+    *n_triangles = (uint32_t)nt;
     return D2R_OK;
 }

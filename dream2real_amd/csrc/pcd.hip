@@ -282,6 +282,12 @@ int pcd_candidates(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const Pcd
 
 }  // namespace
 
+int d2r_pcd_check_view(d2r_ctx *ctx, const d2r_pcd_view *view)
+{
+    PcdCam c;
+    return check_view(ctx, view, c);
+}
+
 extern "C" {
 
 int d2r_pcd_create(d2r_ctx *ctx, const float *xyz, const uint8_t *rgb, uint32_t n, d2r_pcd **out)

@@ -8,8 +8,9 @@ The models the reference downloads enter from outside: segmentation (SAM, XMem) 
 the XMem_masks cache, captioning as a `captions` list or the captions.json cache, the LLM as a `lang_model` object (any
 object with `parse_instr`, `get_movable_obj_idx`, `get_relevant_obj_idxs`; `CachedLangModel` answers from a JSON file), CLIP
 as `scorer` (+ text embeddings, or a text encoder and tokenizer).  NeRF training still raises: camera poses come from
-opt_cam_poses.npy or, with `use_vis_pcds`, from poses.txt, and NeRF visual models from their snapshot cache.  What comes
-after the path (cost-volume visualisation, robot execution) stays outside it.  `ctx` (an
+opt_cam_poses.npy or, with `use_vis_pcds`, from poses.txt, and NeRF visual models from their snapshot cache.  The
+cost-volume and best-pose pictures that follow the path (:360-400) are an option of `dream_best_pose` (`vis_cost_vol`); robot
+execution stays outside.  `ctx` (an
 engine.Context) stands where the reference talks to PyBullet, Open3D and pyngp.
 """
 from __future__ import annotations
@@ -303,10 +304,48 @@ class ImaginationEngine:
         return TaskModel(user_instr, goal_caption, norm_captions, self.scene_model, movable_obj, task_bground_obj, task_bground_masks,
                          self.topdown)
 
-    def dream_best_pose(self, task_model):
+    def _vis_view(self, task_model):
+        """The view of the two pictures: the first render view's OpenCV pose, the scene's intrinsics scaled from the sensor's
+        width x height to cfg.resolution (pixel centres at whole numbers: c' = (c + 0.5) s - 0.5)."""
+        from . import _lib, geometry_utils
+        from .virtual_cam_pose_sample import get_virtual_cam_poses
+        cfg = self.cfg
+        W, H = cfg.resolution if cfg.resolution is not None else combined_rendering.renderer.resolution
+        K = np.asarray(task_model.scene_model.intrinsics, np.float64)
+        sx, sy = W / cfg.width, H / cfg.height
+        view = _lib.PcdView(int(W), int(H), K[0, 0] * sx, K[1, 1] * sy, (K[0, 2] + 0.5) * sx - 0.5, (K[1, 2] + 0.5) * sy - 0.5, 1.0,
+                            geometry_utils.VIS_NEAR)
+        return view, get_virtual_cam_poses(task_model, list(cfg.render_cam_pose_idx))[0]
+
+    def _vis_best_pose(self, task_model, best_pose, pose_batch, pose_scores):
+        """reference dream2real.py:360-400 with tsdf_vis: cost_volume.png (not with use_vis_pcds, as there) and best_pose_vis.png
+        into data_dir, rotated like best_render.png; rank 0 writes."""
+        from . import _lib, geometry_utils
+        from .dist import process_rank
+        if process_rank() != 0:
+            return
+        cfg = self.cfg
+        bground_geoms = [os.path.join(self.data_dir, "phys_mod/mesh_concave_0.obj")]
+        movable_geom = os.path.join(self.data_dir, "phys_mod/mesh_concave_1.obj")
+        for path in bground_geoms + [movable_geom]:
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"dream_best_pose(vis_cost_vol=True) draws {path}, which is missing")
+        view, cam_pose = self._vis_view(task_model)
+        rot = lambda frame: np.ascontiguousarray(np.rot90(frame, k=1, axes=(0, 1)))
+        if not cfg.use_vis_pcds:
+            frame = geometry_utils.vis_cost_volume(pose_scores, list(cfg.sample_res), pose_batch, bground_geoms, ctx=self.ctx, view=view,
+                                                   cam_pose=cam_pose)
+            _lib.png_write(rot(frame), os.path.join(self.data_dir, "cost_volume.png"))
+        frame = geometry_utils.vis_best_pose(best_pose, bground_geoms, movable_geom, task_model.movable_obj.pose, ctx=self.ctx, view=view,
+                                             cam_pose=cam_pose)
+        _lib.png_write(rot(frame), os.path.join(self.data_dir, "best_pose_vis.png"))
+
+    def dream_best_pose(self, task_model, vis_cost_vol=False):
         """-> (best_pose [4,4], pose_batch [N,16], pose_scores [N]) as torch tensors; writes goal_pose.txt,
         pose_batch.txt, pose_scores.txt (and best_render.png, cb_render/*.png through the path) into data_dir.
-        reference dream2real.py:286-358 (its cost-volume visualisation, :360-400, is not part of the path)."""
+        reference dream2real.py:286-358.  vis_cost_vol (the reference's :360-400, off by default here: nothing else is
+        written without it): also cost_volume.png and best_pose_vis.png from phys_mod/mesh_concave_{0,1}.obj, on the cached
+        branch too; a missing mesh file is a FileNotFoundError naming it."""
         import torch
         cfg = self.cfg
         unsupcol_check = None
@@ -332,6 +371,8 @@ class ImaginationEngine:
             best_pose = torch.tensor(np.loadtxt(os.path.join(self.data_dir, "goal_pose.txt"))).float()
             pose_batch = torch.tensor(np.loadtxt(os.path.join(self.data_dir, "pose_batch.txt"))).float()
             pose_scores = torch.tensor(np.loadtxt(os.path.join(self.data_dir, "pose_scores.txt"))).float()
+            if vis_cost_vol:
+                self._vis_best_pose(task_model, best_pose, pose_batch, pose_scores)
             return best_pose, pose_batch, pose_scores
         best_pose, pose_batch, pose_scores = clip_scoring.optimise_pose_grid(                    # :343-355
             self.renderer, self.depths_gt, list(cfg.render_cam_pose_idx), task_model, self.data_dir,
@@ -342,4 +383,6 @@ class ImaginationEngine:
         from .dist import process_rank
         if process_rank() == 0:        # pose-sharded runs: every rank holds the same result, one of them writes it
             clip_scoring.save_pose_outputs(self.data_dir, best_pose, pose_batch, pose_scores)     # :356-358
+        if vis_cost_vol:
+            self._vis_best_pose(task_model, best_pose, pose_batch, pose_scores)
         return best_pose, pose_batch, pose_scores

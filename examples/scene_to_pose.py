@@ -1,5 +1,6 @@
 """A scan folder and a settings file in, the best pose out: the three calls of ImaginationEngine.
-    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir
+    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis]
+--vis also writes best_pose_vis.png (and, without use_vis_pcds, cost_volume.png) into the folder.
 The folder holds poses.txt, images/, depth/, XMem_masks/ (use_cache_segs), captions.json and lang_cache.json (a
 CachedLangModel file); clip_dir holds a CLIP checkpoint: model.safetensors, vocab.json, merges.txt."""
 import os
@@ -11,7 +12,8 @@ from dream2real_amd.clip_model import load_clip_safetensors
 from dream2real_amd.dream2real import CachedLangModel, ImaginationEngine, PathConfig
 from dream2real_amd.tokenizer import ClipBpeTokenizer
 
-config_file, data_dir, user_instr, clip_dir = sys.argv[1:5]
+vis = "--vis" in sys.argv[1:]
+config_file, data_dir, user_instr, clip_dir = [a for a in sys.argv[1:] if a != "--vis"][:4]
 cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=True, phys_backend="tsdf")
 ctx = engine.Context(0)
 clip_cfg, state = load_clip_safetensors(os.path.join(clip_dir, "model.safetensors"))
@@ -22,5 +24,5 @@ imagination = ImaginationEngine(cfg, ctx, engine.ClipScorer(ctx, clip_cfg, state
                                 lang_model=CachedLangModel(os.path.join(data_dir, "lang_cache.json")))
 imagination.build_scene_model()
 task_model = imagination.interpret_user_instr(user_instr)
-best_pose, pose_batch, pose_scores = imagination.dream_best_pose(task_model)
+best_pose, pose_batch, pose_scores = imagination.dream_best_pose(task_model, vis_cost_vol=vis)
 print(best_pose)

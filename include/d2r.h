@@ -724,6 +724,34 @@ D2R_API int d2r_tsdf_extract(d2r_tsdf *vol, float weight_threshold, const float 
  * Vertices of dropped triangles stay in the file, as Open3D's remove_triangles_by_mask leaves them.  Host only. */
 D2R_API int d2r_obj_write(const char *path, const float *vertices, uint32_t n_vertices, const uint32_t *triangles,
                           uint32_t n_triangles, const uint8_t *keep);
+/* A Wavefront .obj -> vertices host [nv][3] fp32 and triangles host [nt][3] (0-based).  Reads `v x y z` and `f` lines; a face
+ * index may be negative (counted back from the last vertex read so far) and may carry `/vt/vn` parts, which are ignored; a face of
+ * more than three vertices becomes the fan (0, i, i + 1); `o` and `g` groups (one per convex part in VHACD's files) are
+ * concatenated; every other line is skipped.  *n_vertices / *n_triangles: capacities on entry, counts on return; call once with
+ * both buffers NULL for the counts, then again to fill.  A missing file, an unreadable number or an index out of range is
+ * D2R_ERR_INVALID with a message that names the path (and the line).  A number is read as fp64 and rounded to fp32; the file
+ * d2r_obj_write wrote reads back to exactly the numbers in it.  Host only. */
+D2R_API int d2r_obj_read(const char *path, uint32_t *n_vertices, uint32_t *n_triangles, float *vertices, uint32_t *triangles);
+
+/* ------------------------------------------------- pictures of the cost volume and the best pose
+ *
+ * replaces the windows of reference vision_3d/geometry_utils.py:137-206 (vis_cost_volume) and dream2real.py:392-400
+ * (draw_geometries) with one frame: a triangle soup of coloured items, flat-shaded, and K score cubes drawn over it as a
+ * maximum-intensity projection.  Every step of the rule is integer or IEEE-exact, so the frame is the same bytes on every call.
+ *   view          d2r_pcd_view with d2r_pcd_render's limits (point_size is checked and otherwise unused); no lens
+ *   cam_pose      host [16] fp32 row-major camera-to-world pose, OpenCV convention (rigid)
+ *   verts         host [nv][3] fp32; tris host [nt][3] indices < nv; tri_item host [nt] item of each triangle, < n_items
+ *   item_mats     host [n_items][16] fp32 row-major model matrices; item_rgb host [n_items][3]
+ *   cube_centres  host [K][3] fp32 world frame; cube_half host [K] half-widths; cube_scores host [K], 0 = not drawn
+ *   background    host [3] the colour of pixels nothing covers
+ *   rgb_out       host [h][w][3]; ids_out host [h][w] or NULL: the winning triangle, -1 - cube where a cube shows, INT32_MIN
+ *                 where nothing does
+ * nt = 0 and K = 0 are valid.  D2R_ERR_INVALID, with the outputs untouched: a null array with a non-zero count, a view outside
+ * the limits, a triangle index >= nv, a tri_item >= n_items.  Synchronous. */
+D2R_API int d2r_mesh_render(d2r_ctx *ctx, const d2r_pcd_view *view, const float *cam_pose, const float *verts, uint32_t nv,
+                            const uint32_t *tris, const uint32_t *tri_item, uint32_t nt, const float *item_mats,
+                            const uint8_t *item_rgb, uint32_t n_items, const float *cube_centres, const float *cube_half,
+                            const uint16_t *cube_scores, uint32_t K, const uint8_t *background, uint8_t *rgb_out, int32_t *ids_out);
 
 /* ------------------------------------------------- the physics pre-filter straight from TSDF volumes
  *
