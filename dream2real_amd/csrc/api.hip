@@ -45,6 +45,8 @@ int d2r_fail(d2r_ctx *ctx, int code, const std::string &msg)
     return code;
 }
 
+hipStream_t d2r_stream(const d2r_ctx *ctx) { return ctx->stream; }
+
 int d2r_reserve(d2r_ctx *ctx, d2r_ctx::Buf &b, size_t bytes)
 {
     if (bytes <= b.cap) return D2R_OK;
@@ -326,16 +328,12 @@ void d2r_ctx_destroy(d2r_ctx *c)
                         c->ev_copy[0], c->ev_copy[1]};
     for (hipEvent_t e : evs)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->mask_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->pcdb_ev)
-        if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; k++)
         if (c->frame_host[k]) (void)hipHostFree(c->frame_host[k]);
     if (c->render_stream) (void)hipStreamDestroy(c->render_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;      // the stage timers' events go here, the context's device still current
 }
 
 int d2r_ctx_set_stream(d2r_ctx *ctx, void *s)

@@ -114,8 +114,8 @@ struct d2r_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string err;
-    // growable device workspaces (one per role so sizes are independent)
-    struct Buf { void *p = nullptr; size_t cap = 0; };
+    // growable device workspaces (one per role so sizes are independent); a role with several segments lays them out with D2rStage
+    using Buf = D2rBuf;
     Buf queue2, sort_counts;   // ray sort: the sorted queue, per-chunk bin counts / offsets
     Buf cams, queue, counters, frames, rgba, depth, poses, clipws[8], text, logits, pix;
     // host -> device uploads of small caller buffers on asynchronous entry points (text embeddings of d2r_render_score)
@@ -128,16 +128,14 @@ struct d2r_ctx {
     // background of the current view
     Buf bg_rgba, bg_depth, bg_u8;
     Buf pcd_mats, pcd_bg_keys, pcd_bg_frame, pcd_cols;   // pcd.hip: candidate matrices, background key buffer and colour frame, colour table of the current call
-    Buf mv_in, mv_recs, mv_queue, mv_shade, mv_keys, mv_out;   // meshvis.hip: uploaded inputs, triangle records, the large-triangle queue, shade bytes, mesh + cube key buffers, rgb + ids of the current call
-    Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots, result frames, union-find parents + component statistics of a pass
-    hipEvent_t mask_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... upload / kernels / download boundaries of the last batch call (d2r_masks_get_timing)
-    bool mask_timed = false;
-    hipEvent_t pcdb_ev[3] = {nullptr, nullptr, nullptr};   // pcdbuild.hip: upload / kernels boundaries of the last d2r_pcd_build (d2r_pcd_build_get_timing)
-    bool pcdb_timed = false;
+    Buf mv_in, mv_recs, mv_queue, mv_shade, mv_keys, mv_out;   // meshvis.hip: uploaded inputs (seven segments of a D2rStage), triangle records, the large-triangle queue, shade bytes, mesh + cube key buffers, rgb + ids of the current call
+    Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots (the segments of a D2rStage per entry point), result frames, union-find parents + component statistics of a pass
+    D2rStageTimer mask_timer;    // ... upload / kernels / download of the last batch call (d2r_masks_get_timing)
+    D2rStageTimer pcdb_timer;    // pcdbuild.hip: upload / kernels of the last d2r_pcd_build (d2r_pcd_build_get_timing)
     Buf lens_tab;                // undistorted camera-space directions of the current view's pixels (nerf.hip lens_table)
     float lens_key[10] = {};     // ... and the view (size, intrinsics, coefficients) it was computed for
     bool lens_key_valid = false;
-    Buf rect_ws;                 // d2r_rectify_background_depth: source images, tap tables, outputs
+    Buf rect_ws;                 // d2r_rectify_background_depth: source images, tap tables, outputs (one D2rStage)
     Buf rects;                   // per candidate of a pass: frame rectangle (x0, y0, x1, y1) its rays were generated in
     Buf bg_patches;              // CLIP patches of the background frame itself (one image)
     const void *bg_patches_for = nullptr;   // the d2r_clip they were computed with (nullptr = stale)
@@ -235,7 +233,6 @@ struct PerDeviceOnce {
     void run(int device, F &&fn) { std::call_once(flag[device % D2R_MAX_DEVICES], fn); }
 };
 
-int d2r_reserve(d2r_ctx *ctx, d2r_ctx::Buf &b, size_t bytes);
 int d2r_pcd_check_view(d2r_ctx *ctx, const d2r_pcd_view *view);      // pcd.hip: the limits d2r_pcd_render holds a view to (meshvis.hip shares them)
 
 // phys.hip: the host side the two physics pre-filters (hulls + GJK in phys.hip, points against the TSDF field in sdfphys.hip) share
@@ -251,14 +248,6 @@ int d2r_upload_text(d2r_ctx *, const d2r_clip *, const float *text, uint32_t C);
 int d2r_score_frames_chunked(d2r_ctx *, const d2r_clip *, uint32_t n, uint32_t w, uint32_t h, int rot90, uint32_t C, float logit_scale,
                              const std::function<int(uint32_t c0, uint32_t nc)> &fill, float *logits_out, float *embeds_out /* optional */,
                              uint8_t *frames_out /* optional */);
-
-#define D2R_HIP(ctx, expr)                                                              \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return d2r_fail(ctx, D2R_ERR_DEVICE,                                        \
-                            std::string(#expr) + ": " + hipGetErrorString(e_));         \
-    } while (0)
 
 // nerf.hip launchers
 int d2r_launch_cameras_direct(d2r_ctx *, const ViewParams &, const float *cams_nerf_dev, uint32_t n,

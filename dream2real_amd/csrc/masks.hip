@@ -476,23 +476,6 @@ int masks_check_frames(d2r_ctx *ctx, uint32_t n, uint32_t w, uint32_t h)
     return D2R_OK;
 }
 
-int masks_check_cam(d2r_ctx *ctx, const float *poses, uint32_t n, const double *K)
-{
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(K[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "masks: intrinsics must be finite");
-    if (K[0] == 0.0 || K[4] == 0.0) return d2r_fail(ctx, D2R_ERR_INVALID, "masks: focal lengths must not be 0");
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(poses[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "masks: poses must be finite");
-    return D2R_OK;
-}
-
-int masks_events(d2r_ctx *ctx)
-{
-    for (auto &e : ctx->mask_ev)
-        if (!e) D2R_HIP(ctx, hipEventCreate(&e));
-    return D2R_OK;
-}
-
 // label, flatten and accumulate nf frames whose images start at mask / depth; parent and stats are the pass's workspace
 void masks_label(d2r_ctx *ctx, const uint8_t *mask, const uint16_t *depth, uint32_t nf, uint32_t w, uint32_t h, uint32_t *parent,
                  unsigned long long *stats)
@@ -530,24 +513,21 @@ int d2r_scene_bound_masks(d2r_ctx *ctx, const uint16_t *depth_u16, uint32_t n, u
     if (!depth_u16 || !poses || !K || !bounds || !out_u8) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
     if (window < 1 || window > 64) return d2r_fail(ctx, D2R_ERR_INVALID, "scene-bound masks: window must be 1 .. 64");
     int rc;
-    if ((rc = masks_check_frames(ctx, n, w, h)) || (rc = masks_check_cam(ctx, poses, n, K))) return rc;
+    if ((rc = masks_check_frames(ctx, n, w, h)) || (rc = d2r_check_cam(ctx, "masks", K, poses, n))) return rc;
     for (int i = 0; i < 6; ++i)
         if (std::isnan(bounds[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "scene-bound masks: bounds must not be NaN");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = masks_events(ctx))) return rc;
     const size_t px = (size_t)w * h, ww = (w + 63) / 64, words = (size_t)n * h * ww;
-    const size_t o_pose = (px * 2 * n + 255) & ~(size_t)255, o_bits = (o_pose + (size_t)n * 64 + 255) & ~(size_t)255;
-    if ((rc = d2r_reserve(ctx, ctx->mask_in, o_bits + 2 * words * 8)) || (rc = d2r_reserve(ctx, ctx->mask_out, px * n))) return rc;
-    uint8_t *base = (uint8_t *)ctx->mask_in.p;
-    const uint16_t *d_depth = (const uint16_t *)base;
-    const float *d_pose = (const float *)(base + o_pose);
-    unsigned long long *b0 = (unsigned long long *)(base + o_bits), *b1 = b0 + words;
+    D2rStage in(ctx, ctx->mask_in);
+    const size_t o_depth = in.add(px * 2 * n), o_pose = in.add((size_t)n * 64), o_bits = in.add(2 * words * 8);
+    if ((rc = in.reserve()) || (rc = d2r_reserve(ctx, ctx->mask_out, px * n))) return rc;
+    const uint16_t *d_depth = in.at<uint16_t>(o_depth);
+    const float *d_pose = in.at<float>(o_pose);
+    unsigned long long *b0 = in.at<unsigned long long>(o_bits), *b1 = b0 + words;
     MaskCam c{K[0], K[4], K[2], K[5]};
     MaskBox b{{bounds[0], bounds[1], -100.0}, {bounds[3], bounds[4], bounds[5]}};       // the reference overwrites zmin (data_loader.py:84)
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[0], ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(base, depth_u16, px * 2 * n, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(base + o_pose, poses, (size_t)n * 64, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[1], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 0)) || (rc = in.upload(o_depth, depth_u16, px * 2 * n))) return rc;
+    if ((rc = in.upload(o_pose, poses, (size_t)n * 64)) || (rc = ctx->mask_timer.mark(ctx, 1))) return rc;
     const uint32_t wpf = (uint32_t)(h * ww), W8 = (w + 7) / 8;
     const dim3 g_unpack((uint32_t)(((size_t)h * W8 + MK_THREADS - 1) / MK_THREADS), n);
     hipLaunchKernelGGL(k_scene_bounds, dim3((wpf + 3) / 4, n), dim3(MK_THREADS), 0, ctx->stream, d_depth, d_pose, c, b, (int)w, (int)h, (int)ww, b0);
@@ -562,11 +542,11 @@ int d2r_scene_bound_masks(d2r_ctx *ctx, const uint16_t *depth_u16, uint32_t n, u
     hipLaunchKernelGGL(k_unpack, g_unpack, dim3(MK_THREADS), 0, ctx->stream, (const unsigned long long *)b0, (int)w, (int)h, (int)ww,
                        (uint8_t *)ctx->mask_out.p);
     D2R_HIP(ctx, hipGetLastError());
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[2], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 2))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(out_u8, ctx->mask_out.p, px * n, hipMemcpyDeviceToHost, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[3], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 3))) return rc;
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->mask_timed = true;
+    ctx->mask_timer.done();
     return D2R_OK;
 }
 
@@ -581,39 +561,33 @@ int d2r_masks_prune(d2r_ctx *ctx, int mode, const uint8_t *masks_u8, const uint1
     MaskCam c{1.0, 1.0, 0.0, 0.0};
     MaskCentre ctr{{0.0, 0.0, 0.0}};
     if (mode == 0) {
-        if ((rc = masks_check_cam(ctx, poses, n, K))) return rc;
+        if ((rc = d2r_check_cam(ctx, "masks", K, poses, n))) return rc;
         for (int i = 0; i < 3; ++i)
             if (!std::isfinite(centre[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "masks prune: scene centre must be finite");
         c = MaskCam{K[0], K[4], K[2], K[5]};
         ctr = MaskCentre{{centre[0], centre[1], centre[2]}};
     }
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = masks_events(ctx))) return rc;
     const size_t px = (size_t)w * h, tot = px * n;
     const bool have_depth = mode == 0;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_depth = up(tot), o_oob = o_depth + up(have_depth ? tot * 2 : 0), o_pose = o_oob + up(oob_u8 ? tot : 0),
-                 o_n = o_pose + up((size_t)n * 64), o_key = o_n + up((size_t)n * 1024), o_best = o_key + up((size_t)n * 1024),
-                 in_total = o_best + up((size_t)n * 2048);
+    D2rStage in(ctx, ctx->mask_in);      // a frame set the call goes without is a segment of 0 bytes
+    const size_t o_mask = in.add(tot), o_depth = in.add(have_depth ? tot * 2 : 0), o_oob = in.add(oob_u8 ? tot : 0),
+                 o_pose = in.add((size_t)n * 64), o_n = in.add((size_t)n * 1024), o_key = in.add((size_t)n * 1024),
+                 o_best = in.add((size_t)n * 2048);
     const uint32_t per = masks_pass_frames(n, px);
-    if ((rc = d2r_reserve(ctx, ctx->mask_in, in_total)) || (rc = d2r_reserve(ctx, ctx->mask_out, tot)) ||
+    if ((rc = in.reserve()) || (rc = d2r_reserve(ctx, ctx->mask_out, tot)) ||
         (rc = d2r_reserve(ctx, ctx->mask_ws, (size_t)per * px * (4 + 8 * ST_WORDS))))
         return rc;
-    uint8_t *base = (uint8_t *)ctx->mask_in.p;
-    const uint8_t *d_mask = base, *d_oob = oob_u8 ? base + o_oob : nullptr;
-    const uint16_t *d_depth = have_depth ? (const uint16_t *)(base + o_depth) : nullptr;
-    const float *d_pose = (const float *)(base + o_pose);
-    SelSlots S{(uint32_t *)(base + o_n), (uint32_t *)(base + o_key), (unsigned long long *)(base + o_best)};
+    const uint8_t *d_mask = in.at<uint8_t>(o_mask), *d_oob = oob_u8 ? in.at<uint8_t>(o_oob) : nullptr;
+    const uint16_t *d_depth = have_depth ? in.at<uint16_t>(o_depth) : nullptr;
+    const float *d_pose = in.at<float>(o_pose);
+    SelSlots S{in.at<uint32_t>(o_n), in.at<uint32_t>(o_key), in.at<unsigned long long>(o_best)};
     unsigned long long *stats = (unsigned long long *)ctx->mask_ws.p;
     uint32_t *parent = (uint32_t *)((uint8_t *)ctx->mask_ws.p + (size_t)per * px * 8 * ST_WORDS);
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[0], ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(base, masks_u8, tot, hipMemcpyHostToDevice, ctx->stream));
-    if (have_depth) {
-        D2R_HIP(ctx, hipMemcpyAsync(base + o_depth, depth_u16, tot * 2, hipMemcpyHostToDevice, ctx->stream));
-        D2R_HIP(ctx, hipMemcpyAsync(base + o_pose, poses, (size_t)n * 64, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (oob_u8) D2R_HIP(ctx, hipMemcpyAsync(base + o_oob, oob_u8, tot, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[1], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 0)) || (rc = in.upload(o_mask, masks_u8, tot))) return rc;
+    if (have_depth && ((rc = in.upload(o_depth, depth_u16, tot * 2)) || (rc = in.upload(o_pose, poses, (size_t)n * 64)))) return rc;
+    if (oob_u8 && (rc = in.upload(o_oob, oob_u8, tot))) return rc;
+    if ((rc = ctx->mask_timer.mark(ctx, 1))) return rc;
     hipLaunchKernelGGL(k_select_init, dim3((n * 256u + MK_THREADS - 1) / MK_THREADS), dim3(MK_THREADS), 0, ctx->stream, S, n * 256u, mode);
     const uint32_t gpx = (uint32_t)((px + MK_THREADS - 1) / MK_THREADS);
     for (uint32_t f0 = 0; f0 < n; f0 += per) {              // passes share the workspace; nothing waits in between
@@ -628,11 +602,11 @@ int d2r_masks_prune(d2r_ctx *ctx, int mode, const uint8_t *masks_u8, const uint1
                            (const uint32_t *)parent, mode, f0, S, (uint8_t *)ctx->mask_out.p + (size_t)f0 * px);
     }
     D2R_HIP(ctx, hipGetLastError());
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[2], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 2))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(out_u8, ctx->mask_out.p, tot, hipMemcpyDeviceToHost, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[3], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 3))) return rc;
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->mask_timed = true;
+    ctx->mask_timer.done();
     return D2R_OK;
 }
 
@@ -645,14 +619,13 @@ int d2r_masks_components(d2r_ctx *ctx, const uint8_t *mask_u8, const uint16_t *d
     if ((rc = masks_check_frames(ctx, 1, w, h))) return rc;
     D2R_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)w * h;
-    const size_t o_depth = (px + 255) & ~(size_t)255;
-    if ((rc = d2r_reserve(ctx, ctx->mask_in, o_depth + px * 2)) || (rc = d2r_reserve(ctx, ctx->mask_ws, px * (4 + 8 * ST_WORDS)))) return rc;
-    uint8_t *base = (uint8_t *)ctx->mask_in.p;
+    D2rStage in(ctx, ctx->mask_in);
+    const size_t o_mask = in.add(px), o_depth = in.add(px * 2);
+    if ((rc = in.reserve()) || (rc = d2r_reserve(ctx, ctx->mask_ws, px * (4 + 8 * ST_WORDS)))) return rc;
     unsigned long long *stats = (unsigned long long *)ctx->mask_ws.p;
     uint32_t *parent = (uint32_t *)((uint8_t *)ctx->mask_ws.p + px * 8 * ST_WORDS);
-    D2R_HIP(ctx, hipMemcpyAsync(base, mask_u8, px, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(base + o_depth, depth_u16, px * 2, hipMemcpyHostToDevice, ctx->stream));
-    masks_label(ctx, base, (const uint16_t *)(base + o_depth), 1, w, h, parent, stats);
+    if ((rc = in.upload(o_mask, mask_u8, px)) || (rc = in.upload(o_depth, depth_u16, px * 2))) return rc;
+    masks_label(ctx, in.at<uint8_t>(o_mask), in.at<uint16_t>(o_depth), 1, w, h, parent, stats);
     D2R_HIP(ctx, hipGetLastError());
     std::vector<unsigned long long> st(px * ST_WORDS);
     D2R_HIP(ctx, hipMemcpyAsync(keys_out, parent, px * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -675,18 +648,18 @@ int d2r_masks_lut(d2r_ctx *ctx, const uint8_t *masks_u8, const uint8_t *oob_u8, 
     int rc;
     if ((rc = masks_check_frames(ctx, n, w, h))) return rc;
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t tot = (size_t)w * h * n, seg = (tot + 255) & ~(size_t)255;
-    if ((rc = d2r_reserve(ctx, ctx->mask_in, 2 * seg + 256)) || (rc = d2r_reserve(ctx, ctx->mask_out, 2 * seg))) return rc;
-    uint8_t *base = (uint8_t *)ctx->mask_in.p, *ob = (uint8_t *)ctx->mask_out.p;
-    D2R_HIP(ctx, hipMemcpyAsync(base, masks_u8, tot, hipMemcpyHostToDevice, ctx->stream));
-    if (oob_u8) D2R_HIP(ctx, hipMemcpyAsync(base + seg, oob_u8, tot, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(base + 2 * seg, lut, 256, hipMemcpyHostToDevice, ctx->stream));
+    const size_t tot = (size_t)w * h * n;
+    D2rStage in(ctx, ctx->mask_in), out(ctx, ctx->mask_out);
+    const size_t o_mask = in.add(tot), o_oob = in.add(tot), o_lut = in.add(256), o_out = out.add(tot), o_alpha = out.add(tot);
+    if ((rc = in.reserve()) || (rc = out.reserve())) return rc;
+    if ((rc = in.upload(o_mask, masks_u8, tot)) || (oob_u8 && (rc = in.upload(o_oob, oob_u8, tot))) || (rc = in.upload(o_lut, lut, 256))) return rc;
+    uint8_t *d_out = out.at<uint8_t>(o_out), *d_alpha = alpha_out_u8 ? out.at<uint8_t>(o_alpha) : nullptr;
     const size_t quads = (tot + 3) / 4;
-    hipLaunchKernelGGL(k_mask_lut, dim3((uint32_t)((quads + MK_THREADS - 1) / MK_THREADS)), dim3(MK_THREADS), 0, ctx->stream, (const uint8_t *)base,
-                       oob_u8 ? (const uint8_t *)(base + seg) : nullptr, tot, (const uint8_t *)(base + 2 * seg), ob, alpha_out_u8 ? ob + seg : nullptr);
+    hipLaunchKernelGGL(k_mask_lut, dim3((uint32_t)((quads + MK_THREADS - 1) / MK_THREADS)), dim3(MK_THREADS), 0, ctx->stream,
+                       in.at<const uint8_t>(o_mask), oob_u8 ? in.at<const uint8_t>(o_oob) : nullptr, tot, in.at<const uint8_t>(o_lut), d_out, d_alpha);
     D2R_HIP(ctx, hipGetLastError());
-    D2R_HIP(ctx, hipMemcpyAsync(out_u8, ob, tot, hipMemcpyDeviceToHost, ctx->stream));
-    if (alpha_out_u8) D2R_HIP(ctx, hipMemcpyAsync(alpha_out_u8, ob + seg, tot, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(out_u8, d_out, tot, hipMemcpyDeviceToHost, ctx->stream));
+    if (alpha_out_u8) D2R_HIP(ctx, hipMemcpyAsync(alpha_out_u8, d_alpha, tot, hipMemcpyDeviceToHost, ctx->stream));
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return D2R_OK;
 }
@@ -698,37 +671,28 @@ int d2r_masks_census(d2r_ctx *ctx, const uint8_t *masks_u8, uint32_t n, uint32_t
     int rc;
     if ((rc = masks_check_frames(ctx, n, w, h))) return rc;
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = masks_events(ctx))) return rc;
     const size_t px = (size_t)w * h, tot = px * n, out_bytes = (size_t)n * 256 * sizeof(uint32_t);
-    if ((rc = d2r_reserve(ctx, ctx->mask_in, tot)) || (rc = d2r_reserve(ctx, ctx->mask_out, out_bytes))) return rc;
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[0], ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(ctx->mask_in.p, masks_u8, tot, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[1], ctx->stream));
+    D2rStage in(ctx, ctx->mask_in);
+    const size_t o_mask = in.add(tot);
+    if ((rc = in.reserve()) || (rc = d2r_reserve(ctx, ctx->mask_out, out_bytes))) return rc;
+    if ((rc = ctx->mask_timer.mark(ctx, 0)) || (rc = in.upload(o_mask, masks_u8, tot)) || (rc = ctx->mask_timer.mark(ctx, 1))) return rc;
     D2R_HIP(ctx, hipMemsetAsync(ctx->mask_out.p, 0, out_bytes, ctx->stream));
     const size_t segs = px / 16 + 2;                         // a frame overlaps at most this many aligned segments of the batch
     hipLaunchKernelGGL(k_census, dim3((uint32_t)((segs + CS_SEGS - 1) / CS_SEGS), n), dim3(MK_THREADS), 0, ctx->stream,
-                       (const uint8_t *)ctx->mask_in.p, px, (uint32_t *)ctx->mask_out.p);
+                       in.at<const uint8_t>(o_mask), px, (uint32_t *)ctx->mask_out.p);
     D2R_HIP(ctx, hipGetLastError());
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[2], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 2))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(counts_out, ctx->mask_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->mask_ev[3], ctx->stream));
+    if ((rc = ctx->mask_timer.mark(ctx, 3))) return rc;
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->mask_timed = true;
+    ctx->mask_timer.done();
     return D2R_OK;
 }
 
 int d2r_masks_get_timing(d2r_ctx *ctx, double *ms_out)
 {
     if (!ctx || !ms_out) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
-    if (!ctx->mask_timed) return d2r_fail(ctx, D2R_ERR_INVALID, "masks timing: no batch call has run on this context");
-    float up = 0.f, dev = 0.f, down = 0.f;
-    D2R_HIP(ctx, hipEventElapsedTime(&up, ctx->mask_ev[0], ctx->mask_ev[1]));
-    D2R_HIP(ctx, hipEventElapsedTime(&dev, ctx->mask_ev[1], ctx->mask_ev[2]));
-    D2R_HIP(ctx, hipEventElapsedTime(&down, ctx->mask_ev[2], ctx->mask_ev[3]));
-    ms_out[0] = up;
-    ms_out[1] = dev;
-    ms_out[2] = down;
-    return D2R_OK;
+    return ctx->mask_timer.read(ctx, ms_out, 3, "masks timing: no batch call has run on this context");
 }
 
 }  // extern "C"

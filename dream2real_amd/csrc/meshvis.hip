@@ -308,16 +308,6 @@ __global__ __launch_bounds__(MV_THREADS) void k_mv_resolve(const unsigned long l
     ids[p] = id;
 }
 
-// C = A B, fp64, each entry summed over l = 0, 1, 2, 3 in that order (the order of pcd.hip's mul4)
-void mv_mul4(const double A[16], const double B[16], double C[16])
-{
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            C[i * 4 + j] = ((A[i * 4 + 0] * B[0 * 4 + j] + A[i * 4 + 1] * B[1 * 4 + j]) + A[i * 4 + 2] * B[2 * 4 + j]) + A[i * 4 + 3] * B[3 * 4 + j];
-}
-
-size_t mv_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int d2r_mesh_render(d2r_ctx *ctx, const d2r_pcd_view *view, const float *cam_pose, const float *verts, uint32_t nv,
@@ -343,18 +333,16 @@ extern "C" int d2r_mesh_render(d2r_ctx *ctx, const d2r_pcd_view *view, const flo
     const MvCam c{view->fx, view->fy, view->cx, view->cy, view->near, (int32_t)view->width, (int32_t)view->height};
     // matrices: inv(cam_pose) item_mat in fp64, rounded once; the cubes live in the world frame: inv(cam_pose) alone
     double Ci[16], P[16], T[16];
-    d2r_rigid_inverse(cam_pose, Ci);
-    Ci[12] = Ci[13] = Ci[14] = 0.0;
-    Ci[15] = 1.0;
+    d2r_rigid_inverse4(cam_pose, Ci);
     MvMat cam_mat;
-    for (int i = 0; i < 12; ++i) cam_mat.m[i] = (float)Ci[i];
+    d2r_round34(Ci, cam_mat.m);
     std::vector<MvMat> mats(std::max<uint32_t>(n_items, 1));
     std::vector<uint32_t> cols(std::max<uint32_t>(n_items, 1), 0u);
     for (uint32_t k = 0; k < n_items; ++k) {
-        for (int i = 0; i < 16; ++i) P[i] = (double)item_mats[(size_t)k * 16 + i];
-        mv_mul4(Ci, P, T);
-        for (int i = 0; i < 12; ++i) mats[k].m[i] = (float)T[i];
-        cols[k] = (uint32_t)item_rgb[3 * (size_t)k] | (uint32_t)item_rgb[3 * (size_t)k + 1] << 8 | (uint32_t)item_rgb[3 * (size_t)k + 2] << 16;
+        d2r_load16(item_mats + (size_t)k * 16, P);
+        d2r_mul4(Ci, P, T);
+        d2r_round34(T, mats[k].m);
+        cols[k] = d2r_pack_rgb(item_rgb + 3 * (size_t)k);
     }
     std::vector<float4> cubes(std::max<uint32_t>(K, 1), float4{0.f, 0.f, 0.f, 0.f});
     std::vector<uint32_t> scores(std::max<uint32_t>(K, 1), 0u);
@@ -362,39 +350,35 @@ extern "C" int d2r_mesh_render(d2r_ctx *ctx, const d2r_pcd_view *view, const flo
         cubes[k] = float4{cube_centres[3 * (size_t)k], cube_centres[3 * (size_t)k + 1], cube_centres[3 * (size_t)k + 2], cube_half[k]};
         scores[k] = cube_scores[k];
     }
-    const uint32_t bg = (uint32_t)background[0] | (uint32_t)background[1] << 8 | (uint32_t)background[2] << 16;
+    const uint32_t bg = d2r_pack_rgb(background);
 
     // workspaces (owned by the context, grown and never shrunk): the inputs, the records and the queue, the two key buffers, the outputs
     const size_t px = (size_t)c.W * c.H, nct = (size_t)K * 12, nrec = std::max<size_t>(std::max<size_t>(nt, nct), 1);
-    const size_t o_verts = 0, o_tris = o_verts + mv_align((size_t)nv * 12), o_item = o_tris + mv_align((size_t)nt * 12),
-                 o_mats = o_item + mv_align((size_t)nt * 4), o_cols = o_mats + mv_align(mats.size() * sizeof(MvMat)),
-                 o_cubes = o_cols + mv_align(cols.size() * 4), o_scores = o_cubes + mv_align(cubes.size() * sizeof(float4)),
-                 in_bytes = o_scores + mv_align(scores.size() * 4);
-    if ((rc = d2r_reserve(ctx, ctx->mv_in, in_bytes))) return rc;
+    D2rStage in(ctx, ctx->mv_in);
+    const size_t o_verts = in.add((size_t)nv * 12), o_tris = in.add((size_t)nt * 12), o_item = in.add((size_t)nt * 4),
+                 o_mats = in.add(mats.size() * sizeof(MvMat)), o_cols = in.add(cols.size() * 4), o_cubes = in.add(cubes.size() * sizeof(float4)),
+                 o_scores = in.add(scores.size() * 4);
+    if ((rc = in.reserve())) return rc;
     if ((rc = d2r_reserve(ctx, ctx->mv_recs, nrec * sizeof(MvTri)))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->mv_queue, 256 + nrec * 4))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->mv_shade, std::max<size_t>(nt, 1)))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->mv_keys, px * 16))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->mv_out, px * 4 + px * 3))) return rc;
-    char *in = (char *)ctx->mv_in.p;
     hipStream_t st = ctx->stream;
-    if (nv) D2R_HIP(ctx, hipMemcpyAsync(in + o_verts, verts, (size_t)nv * 12, hipMemcpyHostToDevice, st));
-    if (nt) D2R_HIP(ctx, hipMemcpyAsync(in + o_tris, tris, (size_t)nt * 12, hipMemcpyHostToDevice, st));
-    if (nt) D2R_HIP(ctx, hipMemcpyAsync(in + o_item, tri_item, (size_t)nt * 4, hipMemcpyHostToDevice, st));
-    D2R_HIP(ctx, hipMemcpyAsync(in + o_mats, mats.data(), mats.size() * sizeof(MvMat), hipMemcpyHostToDevice, st));
-    D2R_HIP(ctx, hipMemcpyAsync(in + o_cols, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, st));
-    D2R_HIP(ctx, hipMemcpyAsync(in + o_cubes, cubes.data(), cubes.size() * sizeof(float4), hipMemcpyHostToDevice, st));
-    D2R_HIP(ctx, hipMemcpyAsync(in + o_scores, scores.data(), scores.size() * 4, hipMemcpyHostToDevice, st));
+    if (nv && (rc = in.upload(o_verts, verts, (size_t)nv * 12))) return rc;
+    if (nt && ((rc = in.upload(o_tris, tris, (size_t)nt * 12)) || (rc = in.upload(o_item, tri_item, (size_t)nt * 4)))) return rc;
+    if ((rc = in.upload(o_mats, mats.data(), mats.size() * sizeof(MvMat))) || (rc = in.upload(o_cols, cols.data(), cols.size() * 4))) return rc;
+    if ((rc = in.upload(o_cubes, cubes.data(), cubes.size() * sizeof(float4))) || (rc = in.upload(o_scores, scores.data(), scores.size() * 4))) return rc;
     unsigned long long *mesh_keys = (unsigned long long *)ctx->mv_keys.p, *cube_keys = mesh_keys + px;
     D2R_HIP(ctx, hipMemsetAsync(mesh_keys, 0, px * 16, st));
     MvTri *recs = (MvTri *)ctx->mv_recs.p;
     uint32_t *n_large = (uint32_t *)ctx->mv_queue.p, *large = n_large + 64;
-    const uint32_t *d_scores = (const uint32_t *)(in + o_scores);
+    const uint32_t *d_scores = in.at<const uint32_t>(o_scores);
     if (nt) {
         const dim3 grid((nt + MV_THREADS - 1) / MV_THREADS), block(MV_THREADS);
         D2R_HIP(ctx, hipMemsetAsync(n_large, 0, 4, st));
-        hipLaunchKernelGGL(k_mv_setup_mesh, grid, block, 0, st, (const float *)(in + o_verts), (const uint32_t *)(in + o_tris),
-                           (const uint32_t *)(in + o_item), nt, (const MvMat *)(in + o_mats), c, recs, (uint8_t *)ctx->mv_shade.p, large, n_large);
+        hipLaunchKernelGGL(k_mv_setup_mesh, grid, block, 0, st, in.at<const float>(o_verts), in.at<const uint32_t>(o_tris),
+                           in.at<const uint32_t>(o_item), nt, in.at<const MvMat>(o_mats), c, recs, (uint8_t *)ctx->mv_shade.p, large, n_large);
         hipLaunchKernelGGL(k_mv_raster_small<false>, grid, block, 0, st, (const MvTri *)recs, nt, d_scores, c.W, mesh_keys, cube_keys);
         hipLaunchKernelGGL(k_mv_raster_large<false>, dim3(MV_LARGE_BLOCKS), block, 0, st, (const MvTri *)recs, (const uint32_t *)large,
                            (const uint32_t *)n_large, d_scores, c.W, mesh_keys, cube_keys);
@@ -403,7 +387,7 @@ extern "C" int d2r_mesh_render(d2r_ctx *ctx, const d2r_pcd_view *view, const flo
         const uint32_t n = (uint32_t)nct;
         const dim3 grid((n + MV_THREADS - 1) / MV_THREADS), block(MV_THREADS);
         D2R_HIP(ctx, hipMemsetAsync(n_large, 0, 4, st));
-        hipLaunchKernelGGL(k_mv_setup_cubes, grid, block, 0, st, (const float4 *)(in + o_cubes), d_scores, n, cam_mat, c, recs, large, n_large);
+        hipLaunchKernelGGL(k_mv_setup_cubes, grid, block, 0, st, in.at<const float4>(o_cubes), d_scores, n, cam_mat, c, recs, large, n_large);
         hipLaunchKernelGGL(k_mv_raster_small<true>, grid, block, 0, st, (const MvTri *)recs, n, d_scores, c.W, mesh_keys, cube_keys);
         hipLaunchKernelGGL(k_mv_raster_large<true>, dim3(MV_LARGE_BLOCKS), block, 0, st, (const MvTri *)recs, (const uint32_t *)large,
                            (const uint32_t *)n_large, d_scores, c.W, mesh_keys, cube_keys);
@@ -412,7 +396,7 @@ extern "C" int d2r_mesh_render(d2r_ctx *ctx, const d2r_pcd_view *view, const flo
     uint8_t *d_rgb = (uint8_t *)(d_ids + px);
     hipLaunchKernelGGL(k_mv_resolve, dim3((uint32_t)((px + MV_THREADS - 1) / MV_THREADS)), dim3(MV_THREADS), 0, st,
                        (const unsigned long long *)mesh_keys, (const unsigned long long *)cube_keys, (uint32_t)px,
-                       (const uint32_t *)(in + o_item), (const uint32_t *)(in + o_cols), (const uint8_t *)ctx->mv_shade.p, bg, d_rgb, d_ids);
+                       in.at<const uint32_t>(o_item), in.at<const uint32_t>(o_cols), (const uint8_t *)ctx->mv_shade.p, bg, d_rgb, d_ids);
     D2R_HIP(ctx, hipGetLastError());
     D2R_HIP(ctx, hipMemcpyAsync(rgb_out, d_rgb, px * 3, hipMemcpyDeviceToHost, st));
     if (ids_out) D2R_HIP(ctx, hipMemcpyAsync(ids_out, d_ids, px * 4, hipMemcpyDeviceToHost, st));

@@ -183,34 +183,7 @@ __global__ __launch_bounds__(PCD_THREADS) void k_pcd_candidates(const float4 *__
 
 // ------------------------------------------------------------------------------------------------ host side
 
-// d2r_rigid_inverse as a 4x4 for mul4
-void rigid_inverse4(const float *T, double out[16])
-{
-    d2r_rigid_inverse(T, out);
-    out[12] = out[13] = out[14] = 0.0;
-    out[15] = 1.0;
-}
-
-// C = A B, fp64, each entry summed over l = 0, 1, 2, 3 in that order
-void mul4(const double A[16], const double B[16], double C[16])
-{
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            C[i * 4 + j] = ((A[i * 4 + 0] * B[0 * 4 + j] + A[i * 4 + 1] * B[1 * 4 + j]) + A[i * 4 + 2] * B[2 * 4 + j]) +
-                           A[i * 4 + 3] * B[3 * 4 + j];
-}
-
-PcdMat to_mat34(const double T[16])
-{
-    PcdMat M;
-    for (int i = 0; i < 12; ++i) M.m[i] = (float)T[i];
-    return M;
-}
-
-void load16(const float *p, double out[16])
-{
-    for (int i = 0; i < 16; ++i) out[i] = (double)p[i];
-}
+PcdMat to_mat34(const double T[16]) { PcdMat M; d2r_round34(T, M.m); return M; }
 
 int check_view(d2r_ctx *ctx, const d2r_pcd_view *v, PcdCam &c)
 {
@@ -241,13 +214,13 @@ int pcd_prepare(d2r_ctx *ctx, const d2r_pcd *bg, const d2r_pcd *mv, const d2r_pc
         return d2r_fail(ctx, D2R_ERR_INVALID, "background + movable points must stay below 2^32 - 1");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
     double Ci[16], Oi[16], P[16], T[16], M[16];
-    rigid_inverse4(cam_pose, Ci);
-    rigid_inverse4(obj_pose_now, Oi);
+    d2r_rigid_inverse4(cam_pose, Ci);
+    d2r_rigid_inverse4(obj_pose_now, Oi);
     std::vector<PcdMat> mats(std::max<uint32_t>(K, 1));
     for (uint32_t k = 0; k < K; ++k) {
-        load16(obj_poses + (size_t)k * 16, P);
-        mul4(Ci, P, T);
-        mul4(T, Oi, M);
+        d2r_load16(obj_poses + (size_t)k * 16, P);
+        d2r_mul4(Ci, P, T);
+        d2r_mul4(T, Oi, M);
         mats[k] = to_mat34(M);
     }
     const size_t px = (size_t)c.W * c.H;
@@ -299,7 +272,7 @@ int d2r_pcd_create(d2r_ctx *ctx, const float *xyz, const uint8_t *rgb, uint32_t 
     std::vector<uint32_t> col(std::max<uint32_t>(n, 1), 0u);
     for (uint32_t i = 0; i < n; ++i) {
         p[i] = float4{xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.f};
-        col[i] = (uint32_t)rgb[3 * (size_t)i] | (uint32_t)rgb[3 * (size_t)i + 1] << 8 | (uint32_t)rgb[3 * (size_t)i + 2] << 16;
+        col[i] = d2r_pack_rgb(rgb + 3 * (size_t)i);
     }
     std::unique_ptr<d2r_pcd> m(new d2r_pcd);
     m->device = ctx->device;

@@ -370,11 +370,7 @@ int pb_check(const uint8_t *rgb, const uint16_t *depth_u16, const uint8_t *label
         seen[obj_ids[o]] = true;
     }
     if (!(voxel >= 0.0) || !std::isfinite(voxel)) return d2r_fail(none, D2R_ERR_INVALID, "pcd build: voxel must be finite and >= 0");
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(K[i])) return d2r_fail(none, D2R_ERR_INVALID, "pcd build: intrinsics must be finite");
-    if (K[0] == 0.0 || K[4] == 0.0) return d2r_fail(none, D2R_ERR_INVALID, "pcd build: focal lengths must not be 0");
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(cam_poses[i])) return d2r_fail(none, D2R_ERR_INVALID, "pcd build: poses must be finite");
+    if (int rc = d2r_check_cam(none, "pcd build", K, cam_poses, n)) return rc;
     for (int i = 0; i < 6; ++i)
         if (std::isnan(bounds[i])) return d2r_fail(none, D2R_ERR_INVALID, "pcd build: bounds must not be NaN");
     if (voxel > 0.0)
@@ -404,8 +400,6 @@ int d2r_pcd_build(d2r_ctx *ctx, const uint8_t *rgb, const uint16_t *depth_u16, c
     if (rc) return d2r_fail(ctx, rc, d2r_last_error(nullptr));      // the message into the context too
     if (!ctx) return d2r_fail(ctx, D2R_ERR_INVALID, "null context");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    for (auto &e : ctx->pcdb_ev)
-        if (!e) D2R_HIP(ctx, hipEventCreate(&e));
     const uint32_t px = w * h, bpf = pb_blocks(px), S = n_objs * n_views, nblk = S * bpf;
     const size_t tot = (size_t)n * px;
 
@@ -428,7 +422,7 @@ int d2r_pcd_build(d2r_ctx *ctx, const uint8_t *rgb, const uint16_t *depth_u16, c
         return rc;
     uint32_t *total = d_small.get(), *maxidx = d_small.get() + 1, *nruns = d_small.get() + 4;
 
-    D2R_HIP(ctx, hipEventRecord(ctx->pcdb_ev[0], ctx->stream));
+    if ((rc = ctx->pcdb_timer.mark(ctx, 0))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(d_rgb.get(), rgb, tot * 3, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(d_depth.get(), depth_u16, tot * 2, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(d_labels.get(), labels, tot, hipMemcpyHostToDevice, ctx->stream));
@@ -436,7 +430,7 @@ int d2r_pcd_build(d2r_ctx *ctx, const uint8_t *rgb, const uint16_t *depth_u16, c
     D2R_HIP(ctx, hipMemcpyAsync(d_views.get(), views, (size_t)n_views * 4, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(d_ids.get(), obj_ids, n_objs, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemsetAsync(d_small.get(), 0, 64, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(ctx->pcdb_ev[1], ctx->stream));
+    if ((rc = ctx->pcdb_timer.mark(ctx, 1))) return rc;
 
     // erosion, then the points of every segment counted
     hipLaunchKernelGGL(k_pb_erode_rows, dim3(bpf, n_views), dim3(PB_THREADS), 0, ctx->stream, (const uint8_t *)d_labels.get(), (const uint32_t *)d_views.get(),
@@ -536,9 +530,9 @@ int d2r_pcd_build(d2r_ctx *ctx, const uint8_t *rgb, const uint16_t *depth_u16, c
                                (const PbOut *)d_outs.get());
         D2R_HIP(ctx, hipGetLastError());
     }
-    D2R_HIP(ctx, hipEventRecord(ctx->pcdb_ev[2], ctx->stream));
+    if ((rc = ctx->pcdb_timer.mark(ctx, 2))) return rc;
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));       // `outs` (pageable host memory) has been consumed, the clouds are complete
-    ctx->pcdb_timed = true;
+    ctx->pcdb_timer.done();
     for (uint32_t o = 0; o < n_objs; ++o) out[o] = clouds[o].release();
     return D2R_OK;
 }
@@ -575,13 +569,7 @@ int d2r_pcd_read(d2r_ctx *ctx, const d2r_pcd *pcd, float *xyz, uint8_t *rgb)
 int d2r_pcd_build_get_timing(d2r_ctx *ctx, double *ms_out)
 {
     if (!ctx || !ms_out) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
-    if (!ctx->pcdb_timed) return d2r_fail(ctx, D2R_ERR_INVALID, "pcd build timing: no d2r_pcd_build has completed on this context");
-    float up = 0.f, dev = 0.f;
-    D2R_HIP(ctx, hipEventElapsedTime(&up, ctx->pcdb_ev[0], ctx->pcdb_ev[1]));
-    D2R_HIP(ctx, hipEventElapsedTime(&dev, ctx->pcdb_ev[1], ctx->pcdb_ev[2]));
-    ms_out[0] = up;
-    ms_out[1] = dev;
-    return D2R_OK;
+    return ctx->pcdb_timer.read(ctx, ms_out, 2, "pcd build timing: no d2r_pcd_build has completed on this context");
 }
 
 }  // extern "C"

@@ -131,32 +131,25 @@ extern "C" int d2r_rectify_background_depth(d2r_ctx *ctx, const void *depth, int
     const AxisTable tx = axis_table(S, W), ty = axis_table(S, H);
     const size_t esz = depth_is_fp16 ? 2 : 4, n_src = (size_t)src_w * src_h, n_dst = (size_t)W * H;
     // one staging allocation: source images, six tables, outputs
-    const size_t o_depth = 0, o_mask = o_depth + ((n_src * esz + 15) & ~(size_t)15), o_tab = o_mask + ((n_src + 15) & ~(size_t)15);
     const size_t tab_x = (size_t)W * 16, tab_y = (size_t)H * 16;
-    const size_t o_out = o_tab + 3 * tab_x + 3 * tab_y, o_mout = o_out + n_dst * 4, total = o_mout + ((n_dst + 15) & ~(size_t)15);
+    D2rStage ws(ctx, ctx->rect_ws);
+    const size_t o_depth = ws.add(n_src * esz), o_mask = ws.add(n_src), o_xt = ws.add(tab_x), o_xc = ws.add(tab_x), o_xi = ws.add(tab_x),
+                 o_yt = ws.add(tab_y), o_yc = ws.add(tab_y), o_yi = ws.add(tab_y), o_out = ws.add(n_dst * 4), o_mout = ws.add(n_dst);
     int rc;
-    if ((rc = d2r_reserve(ctx, ctx->rect_ws, total))) return rc;
-    uint8_t *base = (uint8_t *)ctx->rect_ws.p;
-    D2R_HIP(ctx, hipMemcpyAsync(base + o_depth, depth, n_src * esz, hipMemcpyHostToDevice, ctx->stream));
-    if (mask) D2R_HIP(ctx, hipMemcpyAsync(base + o_mask, mask, n_src, hipMemcpyHostToDevice, ctx->stream));
-    uint8_t *t = base + o_tab;
-    D2R_HIP(ctx, hipMemcpyAsync(t, tx.tap.data(), tab_x, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(t + tab_x, tx.cf.data(), tab_x, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(t + 2 * tab_x, tx.ci.data(), tab_x, hipMemcpyHostToDevice, ctx->stream));
-    uint8_t *u = t + 3 * tab_x;
-    D2R_HIP(ctx, hipMemcpyAsync(u, ty.tap.data(), tab_y, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(u + tab_y, ty.cf.data(), tab_y, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipMemcpyAsync(u + 2 * tab_y, ty.ci.data(), tab_y, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ws.reserve()) || (rc = ws.upload(o_depth, depth, n_src * esz)) || (mask && (rc = ws.upload(o_mask, mask, n_src))) ||
+        (rc = ws.upload(o_xt, tx.tap.data(), tab_x)) || (rc = ws.upload(o_xc, tx.cf.data(), tab_x)) || (rc = ws.upload(o_xi, tx.ci.data(), tab_x)) ||
+        (rc = ws.upload(o_yt, ty.tap.data(), tab_y)) || (rc = ws.upload(o_yc, ty.cf.data(), tab_y)) || (rc = ws.upload(o_yi, ty.ci.data(), tab_y)))
+        return rc;
     // the host vectors above must outlive the copies: pageable-memory copies are staged before the call returns, and
     // the stream is synchronised below before they go out of scope in any case
-    hipLaunchKernelGGL(k_rectify, dim3((uint32_t)((n_dst + 255) / 256)), dim3(256), 0, ctx->stream, (const void *)(base + o_depth),
-                       depth_is_fp16, mask ? (const uint8_t *)(base + o_mask) : (const uint8_t *)nullptr, src_w, x0, y0, W, H,
-                       (const int4 *)t, (const float4 *)(t + tab_x), (const int4 *)(t + 2 * tab_x), (const int4 *)u,
-                       (const float4 *)(u + tab_y), (const int4 *)(u + 2 * tab_y), (float *)(base + o_out),
-                       mask_out ? base + o_mout : (uint8_t *)nullptr, 100.0f);
+    hipLaunchKernelGGL(k_rectify, dim3((uint32_t)((n_dst + 255) / 256)), dim3(256), 0, ctx->stream, ws.at<const void>(o_depth),
+                       depth_is_fp16, mask ? ws.at<const uint8_t>(o_mask) : (const uint8_t *)nullptr, src_w, x0, y0, W, H,
+                       ws.at<const int4>(o_xt), ws.at<const float4>(o_xc), ws.at<const int4>(o_xi), ws.at<const int4>(o_yt),
+                       ws.at<const float4>(o_yc), ws.at<const int4>(o_yi), ws.at<float>(o_out),
+                       mask_out ? ws.at<uint8_t>(o_mout) : (uint8_t *)nullptr, 100.0f);
     D2R_HIP(ctx, hipGetLastError());
-    D2R_HIP(ctx, hipMemcpyAsync(depth_out, base + o_out, n_dst * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (mask_out) D2R_HIP(ctx, hipMemcpyAsync(mask_out, base + o_mout, n_dst, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipMemcpyAsync(depth_out, ws.at<float>(o_out), n_dst * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (mask_out) D2R_HIP(ctx, hipMemcpyAsync(mask_out, ws.at<uint8_t>(o_mout), n_dst, hipMemcpyDeviceToHost, ctx->stream));
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return D2R_OK;
 }

@@ -37,13 +37,7 @@ struct d2r_sdfphys {
     D2rDev<uint32_t> d_coarse;      // [ceil(blocks / 32)] bit (bz ncby + by) ncbx + bx
     D2rDev<float> d_pts;            // [3][n_points] x, y, z of the movable points (SoA), world frame at the initial pose
     uint32_t n_points = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // upload / kernel / download boundaries of the last check
-    bool timed = false;
-    ~d2r_sdfphys()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    D2rStageTimer timer;            // upload / kernel / download of the last check
 };
 
 struct SdfCheckParams {
@@ -214,7 +208,6 @@ int d2r_sdfphys_create(d2r_ctx *ctx, const int32_t *b0, const uint32_t *nv, floa
     if ((rc = h->d_words.alloc(ctx, n_words * 4, "the physics field")) || (rc = h->d_coarse.alloc(ctx, (size_t)n_cwords * 4, "the physics field")) ||
         (rc = h->d_pts.alloc(ctx, soa.size() * 4, "the physics field")))
         return rc;
-    for (int k = 0; k < 4; ++k) D2R_HIP(ctx, hipEventCreate(&h->ev[k]));
     D2R_HIP(ctx, hipMemcpyAsync(h->d_words.get(), field.data(), n_words * 4, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(h->d_pts.get(), soa.data(), soa.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_sdf_coarse, dim3((n_cwords + 3) / 4), dim3(SDF_THREADS), 0, ctx->stream, (const uint32_t *)h->d_words.get(), G, n_blocks,
@@ -261,33 +254,27 @@ int d2r_sdfphys_check(d2r_ctx *ctx, d2r_sdfphys *h, const d2r_phys_params *prm, 
     if ((rc = d2r_reserve(ctx, ctx->poses, (size_t)N * 64))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->pix, (size_t)N + oris + 64))) return rc;
     uint8_t *d_valid = (uint8_t *)ctx->pix.p, *d_mask = d_valid + ((N + 63) / 64) * 64;
-    D2R_HIP(ctx, hipEventRecord(h->ev[0], ctx->stream));
+    if ((rc = h->timer.mark(ctx, 0))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(ctx->poses.p, pose_batch, (size_t)N * 64, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(d_valid, valid_io, N, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(d_mask, mask.data(), oris, hipMemcpyHostToDevice, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(h->ev[1], ctx->stream));
+    if ((rc = h->timer.mark(ctx, 1))) return rc;
     hipLaunchKernelGGL(k_sdf_check, dim3((N + 3) / 4), dim3(SDF_THREADS), 0, ctx->stream, P, h->G, (const float *)ctx->poses.p, N,
                        (const uint8_t *)d_mask, (const uint32_t *)h->d_words.get(), (const uint32_t *)h->d_coarse.get(), (const float *)h->d_pts.get(), h->n_points,
                        d_valid);
     D2R_HIP(ctx, hipGetLastError());
-    D2R_HIP(ctx, hipEventRecord(h->ev[2], ctx->stream));
+    if ((rc = h->timer.mark(ctx, 2))) return rc;
     D2R_HIP(ctx, hipMemcpyAsync(valid_io, d_valid, N, hipMemcpyDeviceToHost, ctx->stream));
-    D2R_HIP(ctx, hipEventRecord(h->ev[3], ctx->stream));
+    if ((rc = h->timer.mark(ctx, 3))) return rc;
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    h->timed = true;
+    h->timer.done();
     return D2R_OK;
 }
 
 int d2r_sdfphys_get_timing(d2r_ctx *ctx, const d2r_sdfphys *h, double *ms_out)
 {
     if (!ctx || !h || !ms_out) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
-    if (!h->timed) return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_sdfphys_get_timing: no check has run on this handle");
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        D2R_HIP(ctx, hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
-        ms_out[k] = ms;
-    }
-    return D2R_OK;
+    return h->timer.read(ctx, ms_out, 3, "d2r_sdfphys_get_timing: no check has run on this handle");
 }
 
 }  // extern "C"
