@@ -292,12 +292,19 @@ TRI_TABLE = [
 ]
 
 
-def erode(mask, k: int):
-    """cv2.erode(mask, ones((k, k))) with cv2's anchor (k // 2, k // 2) and border rule, written as a direct window minimum."""
+# Wrong rules, one name each: Volume(..., rules={name}) restates the rule with that one departure, so that a test can show that its
+# cases tell the two apart (tests/test_tsdf_edges_host.py).  ("swap_row", r) is given to Volume.triangles() directly.
+WRONG_RULES = ("anchor_low", "border_unset", "z_lt_3", "sdf_le", "zc_ge_0", "rint", "steps_floor", "inside_le", "seven_of_eight",
+               "other_end", "inv_fp32")
+
+
+def erode(mask, k: int, anchor=None, border=True):
+    """cv2.erode(mask, ones((k, k))) with cv2's anchor (k // 2, k // 2) and border rule, written as a direct window minimum.
+    `anchor` and `border` (what a pixel outside the frame counts as) are the rule's; other values restate wrong rules."""
     m = np.asarray(mask).astype(bool)
     H, W = m.shape
-    a = k // 2
-    p = np.ones((H + k - 1, W + k - 1), bool)
+    a = k // 2 if anchor is None else anchor
+    p = np.full((H + k - 1, W + k - 1), bool(border))
     p[a:a + H, a:a + W] = m
     out = np.ones((H, W), bool)
     for di in range(k):
@@ -306,9 +313,9 @@ def erode(mask, k: int):
     return out
 
 
-def rigid_inverse34(T):
-    T = np.asarray(T, np.float32).astype(np.float64).reshape(4, 4)
-    out = np.zeros((3, 4))
+def rigid_inverse34(T, dtype=np.float64):
+    T = np.asarray(T, np.float32).astype(dtype).reshape(4, 4)
+    out = np.zeros((3, 4), dtype)
     for i in range(3):
         for j in range(3):
             out[i, j] = T[j, i]
@@ -317,7 +324,13 @@ def rigid_inverse34(T):
 
 
 class Volume:
-    def __init__(self, bounds, voxel=0.002, trunc=None):
+    def __init__(self, bounds, voxel=0.002, trunc=None, rules=(), probe=False):
+        """rules: names from WRONG_RULES (default: the rule as written).  probe: record in self.probe what the rule touches on
+        its way: per frame the pixels a voxel update read and the number of blocks stamped, band samples that left the grid per
+        face, camera depths met in stamped blocks, and the marching cubes' per-cube table rows."""
+        self.rules = frozenset(rules)
+        assert self.rules <= set(WRONG_RULES), self.rules
+        self.probe = dict(pixels_read=[], frame_blocks=[], steps_outside=np.zeros((3, 2), np.int64), zc_nonpositive=0, zc_zero=0, zc_tiny=0) if probe else None
         self.voxel = f32(voxel)
         self.trunc = f32(8) * self.voxel if trunc is None else f32(trunc)
         b = np.asarray(bounds, np.float64).reshape(2, 3).astype(np.float32).astype(np.float64)
@@ -331,12 +344,15 @@ class Volume:
         self.w = np.zeros((nz, ny, nx), np.float32)
         self.ever = np.zeros((int(self.nb[2]), int(self.nb[1]), int(self.nb[0])), bool)
         self.steps = int(round(float(self.trunc) / float(self.voxel)))
+        if "steps_floor" in self.rules:
+            self.steps = int(np.floor(float(self.trunc) / float(self.voxel)))
         self.frames_used = 0
 
     # ------------------------------------------------------------------------------------------------ frames
     def valid_depth(self, depth_u16, mask, erode_k):
         z = np.asarray(depth_u16, np.uint16).astype(np.float32) / f32(1000)
-        ok = erode(mask, erode_k) & (z > 0) & (z <= DEPTH_MAX)
+        eroded = erode(mask, erode_k, (erode_k - 1) // 2 if "anchor_low" in self.rules else None, "border_unset" not in self.rules)
+        ok = eroded & (z > 0) & ((z < DEPTH_MAX) if "z_lt_3" in self.rules else (z <= DEPTH_MAX))
         return np.where(ok, z, f32(0)).astype(np.float32)
 
     def frame_blocks(self, zbuf, intrinsics, cam_pose):
@@ -358,6 +374,8 @@ class Volume:
             ok = np.ones(len(z), bool)
             for a in range(3):
                 ok &= (g[a] >= lo[a]) & (g[a] < hi[a])
+                if self.probe is not None:
+                    self.probe["steps_outside"][a] += [int((g[a] < lo[a]).sum()), int((g[a] >= hi[a]).sum())]
             b = [(g[a][ok].astype(np.int64) >> 4) - self.b0[a] for a in range(3)]
             out[b[2], b[1], b[0]] = True
         return out
@@ -372,8 +390,11 @@ class Volume:
         self.ever |= blocks
         K = np.asarray(intrinsics, np.float64).reshape(3, 3).astype(np.float32)
         fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
-        Mi = rigid_inverse34(np.asarray(cam_pose, np.float64).reshape(4, 4).astype(np.float32))
+        Mi = rigid_inverse34(np.asarray(cam_pose, np.float64).reshape(4, 4).astype(np.float32), np.float32 if "inv_fp32" in self.rules else np.float64)
         bz, by, bx = np.nonzero(blocks)
+        if self.probe is not None:
+            self.probe["frame_blocks"].append(len(bz))
+            self.probe["pixels_read"].append(np.zeros((H, W), bool))
         o = np.arange(BLOCK)
         for k0 in range(0, len(bz), 512):
             sl = slice(k0, k0 + 512)
@@ -385,17 +406,26 @@ class Volume:
             py = (ly + self.b0[1] * BLOCK).astype(np.float32) * self.voxel
             pz = (lz + self.b0[2] * BLOCK).astype(np.float32) * self.voxel
             xc, yc, zc = (((Mi[r, 0] * px + Mi[r, 1] * py) + Mi[r, 2] * pz) + Mi[r, 3] for r in range(3))
-            ok = zc > 0
+            ok = (zc >= 0) if "zc_ge_0" in self.rules else (zc > 0)
+            if self.probe is not None:
+                self.probe["zc_nonpositive"] += int((zc <= 0).sum())
+                self.probe["zc_zero"] += int((zc == 0).sum())
+                self.probe["zc_tiny"] += int(((zc > 0) & (zc < self.voxel / f32(4))).sum())
             with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-                u = np.floor(((fx * xc) / zc + cx) + f32(0.5))
-                v = np.floor(((fy * yc) / zc + cy) + f32(0.5))
+                if "rint" in self.rules:
+                    u, v = np.rint((fx * xc) / zc + cx), np.rint((fy * yc) / zc + cy)
+                else:
+                    u = np.floor(((fx * xc) / zc + cx) + f32(0.5))
+                    v = np.floor(((fy * yc) / zc + cy) + f32(0.5))
             ok &= (u >= 0) & (u < f32(W)) & (v >= 0) & (v < f32(H))
             ui = np.where(ok, u, 0).astype(np.int64)
             vi = np.where(ok, v, 0).astype(np.int64)
             zp = zbuf[vi, ui]
             ok &= zp > 0
             sdf = zp - zc
-            ok &= ~(sdf < -self.trunc)
+            ok &= ~((sdf <= -self.trunc) if "sdf_le" in self.rules else (sdf < -self.trunc))
+            if self.probe is not None:
+                self.probe["pixels_read"][-1][vi[ok], ui[ok]] = True
             t = np.minimum(sdf / self.trunc, f32(1))
             iz, iy, ix = lz[ok], ly[ok], lx[ok]
             w0, t0 = self.w[iz, iy, ix], self.tsdf[iz, iy, ix]
@@ -421,15 +451,15 @@ class Volume:
         T, Wt = self.tsdf, self.w
         nz, ny, nx = T.shape
         enough = Wt >= f32(weight_threshold)
-        inside = T < 0
+        inside = (T <= 0) if "inside_le" in self.rules else (T < 0)
         sl = lambda d, n: slice(d, n - 1 + d)
-        valid = np.ones((nz - 1, ny - 1, nx - 1), bool)
+        passed = np.zeros((nz - 1, ny - 1, nx - 1), np.int64)
         case = np.zeros((nz - 1, ny - 1, nx - 1), np.int64)
         for c, (dx, dy, dz) in enumerate(CORNERS):
             s = (sl(dz, nz), sl(dy, ny), sl(dx, nx))
-            valid &= enough[s]
+            passed += enough[s]
             case |= inside[s].astype(np.int64) << c
-        case[~valid] = 0
+        case[passed < (7 if "seven_of_eight" in self.rules else 8)] = 0
         case[case == 255] = 0
         cube = np.zeros((nz, ny, nx), np.int64)
         cube[:-1, :-1, :-1] = case
@@ -466,14 +496,28 @@ class Volume:
         for k in range(3):
             m = a == k
             q1 = (g[k][m] + 1 + self.b0[k] * BLOCK).astype(np.float32) * self.voxel
-            verts[m, k] = p0[k][m] + ((q1 - p0[k][m]) * t0[m]) / (t0[m] - t1[m])
+            with np.errstate(invalid="ignore", divide="ignore"):
+                if "other_end" in self.rules:
+                    verts[m, k] = q1 + ((p0[k][m] - q1) * t1[m]) / (t1[m] - t0[m])
+                else:
+                    verts[m, k] = p0[k][m] + ((q1 - p0[k][m]) * t0[m]) / (t0[m] - t1[m])
+        if self.probe is not None:
+            self.probe["cube"], self.probe["vid"] = cube, vid
+        return verts.astype(np.float32), self.triangles(cube, vid)
+
+    @staticmethod
+    def triangles(cube, vid, swap_row=None):
+        """The triangles of the cubes `cube` (table row per voxel, 0: none) as indices `vid` [nz, ny, nx, 3] of their edges' vertices.
+        swap_row: a wrong table, that row's first triangle with its first two indices exchanged."""
         tris = []
         cz, cy, cx = np.nonzero(cube)
         for zz, yy, xx in zip(cz, cy, cx):
             row = TRI_TABLE[cube[zz, yy, xx]]
+            if cube[zz, yy, xx] == swap_row:
+                row = (row[1], row[0]) + row[2:]
             for k in range(0, len(row), 3):
                 tris.append([vid[zz + EDGE_OFF[e][2], yy + EDGE_OFF[e][1], xx + EDGE_OFF[e][0], EDGE_AXIS[e]] for e in row[k:k + 3]])
-        return verts.astype(np.float32), np.asarray(tris, np.int64).reshape(-1, 3)
+        return np.asarray(tris, np.int64).reshape(-1, 3)
 
 
 def clean(verts, tris, crop=None, keep_frac=0.02):
