@@ -98,6 +98,10 @@ PROTOTYPES = {
     "d2r_masks_lut": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr)),
     "d2r_masks_census": (_int, (_ptr, _ptr, _u32, _u32, _u32, _ptr)),
     "d2r_masks_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_thumbs_plan": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_thumbs_fill": (_int, (_ptr, _ptr, _ptr, _u64)),
+    "d2r_thumbs_blur_bits": (_int, (_ptr, _ptr, _u32, _u32, _u32, _ptr)),
+    "d2r_thumbs_get_timing": (_int, (_ptr, _ptr)),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -440,6 +444,56 @@ def masks_timing(ctx):
     """d2r_masks_get_timing -> (upload, kernels, download) of the context's last batch mask call, device-event milliseconds."""
     ms = np.zeros(3, np.float64)
     check(load().d2r_masks_get_timing(_h(ctx), ptr(ms)), _h(ctx))
+    return tuple(float(x) for x in ms)
+
+
+THUMB_REC_WORDS = 10                                    # D2R_THUMB_REC_WORDS: object, frame, flags, area, row0, col0, rows, cols, offset low / high
+THUMB_ACCEPTED, THUMB_CONTAINER, THUMB_ROTATED, THUMB_EDGE, THUMB_SMALL = 1, 2, 4, 8, 16
+
+
+def thumbs_plan(ctx, rgbs, masks, oob, num_objs: int, topdown: bool, multi_view: bool = True, single_view_idx: int = 0,
+                min_area: int = 200, hole_area: int = 400, pad: int = 5, dilate_k: int = 60):
+    """d2r_thumbs_plan: uint8 rgbs [n,h,w,3], labels [n,h,w], out-of-scene masks [n,h,w] -> (records uint32
+    [n_recs, THUMB_REC_WORDS], one per (object, visited frame), total bytes of the packed thumbnails).  The frames stay on the
+    device for thumbs_fill."""
+    c = np.ascontiguousarray(rgbs, np.uint8)
+    m = _frames(masks, np.uint8, "masks")
+    o = _frames(oob, np.uint8, "oob")
+    n, h, w = m.shape
+    if c.shape != (n, h, w, 3) or o.shape != m.shape:
+        raise ValueError(f"rgbs {c.shape}, masks {m.shape} and oob {o.shape} do not describe the same frames")
+    params = np.array([bool(topdown), bool(multi_view), single_view_idx, min_area, hole_area, pad, dilate_k], np.uint32)
+    count = max(int(num_objs) - 1, 0) * (n if multi_view else 1)
+    recs = np.zeros((max(count, 1), THUMB_REC_WORDS), np.uint32)
+    n_recs, total = C.c_uint32(recs.shape[0]), C.c_uint64(0)
+    check(load().d2r_thumbs_plan(_h(ctx), ptr(c), ptr(m), ptr(o), n, w, h, num_objs, ptr(params), ptr(recs), C.byref(n_recs),
+                                 C.byref(total)), _h(ctx))
+    return recs[:n_recs.value], int(total.value)
+
+
+def thumbs_fill(ctx, noise, total: int) -> np.ndarray:
+    """d2r_thumbs_fill: the noise image uint8 [h,w,3] -> the packed thumbnails uint8 [total] of the context's last thumbs_plan; an
+    accepted record's image is out[offset : offset + rows * cols * 3].reshape(rows, cols, 3)."""
+    z = np.ascontiguousarray(noise, np.uint8)
+    out = np.zeros(max(total, 1), np.uint8)
+    check(load().d2r_thumbs_fill(_h(ctx), ptr(z), ptr(out), total), _h(ctx))
+    return out[:total]
+
+
+def thumbs_blur_bits(ctx, bits, dilate_k: int = 60) -> np.ndarray:
+    """d2r_thumbs_blur_bits (parity hook): a 0 / 1 image [h,w] -> its blur bit dilated by dilate_k x dilate_k, uint8 0 / 1."""
+    b = np.ascontiguousarray(bits, np.uint8)
+    if b.ndim != 2:
+        raise ValueError(f"bits must be [h, w], got shape {b.shape}")
+    out = np.empty(b.shape, np.uint8)
+    check(load().d2r_thumbs_blur_bits(_h(ctx), ptr(b), b.shape[1], b.shape[0], dilate_k, ptr(out)), _h(ctx))
+    return out
+
+
+def thumbs_timing(ctx):
+    """d2r_thumbs_get_timing -> (upload, kernels, download) of the context's last thumbs_plan plus thumbs_fill, device-event milliseconds."""
+    ms = np.zeros(3, np.float64)
+    check(load().d2r_thumbs_get_timing(_h(ctx), ptr(ms)), _h(ctx))
     return tuple(float(x) for x in ms)
 
 

@@ -96,6 +96,15 @@ struct ViewParams {
 
 struct ClipParams;   // clip.hip
 
+// masks.hip: what d2r_thumbs_plan leaves for d2r_thumbs_fill.  The frames stay in thumb_in.
+struct D2rThumbPlan {
+    bool valid = false;
+    uint32_t n = 0, w = 0, h = 0, dilate_k = 0;
+    size_t o_rgb = 0, o_mask = 0, o_oob = 0;     // segments of thumb_in
+    uint64_t total = 0;                          // bytes of the packed thumbnails
+    std::vector<uint32_t> recs;                  // [n_recs][D2R_THUMB_REC_WORDS]
+};
+
 // Layer-0 reuse of background tokens inside d2r_render_score (clip.hip "layer-0 reuse"): the frame rectangles the candidates
 // of the chunk touched, and the background's own pre-LayerNorm residual rows and layer-0 q / k / v rows (d2r_clip_layer0_background)
 struct ClipL0Reuse {
@@ -130,6 +139,9 @@ struct d2r_ctx {
     Buf pcd_mats, pcd_bg_keys, pcd_bg_frame, pcd_cols;   // pcd.hip: candidate matrices, background key buffer and colour frame, colour table of the current call
     Buf mv_in, mv_recs, mv_queue, mv_shade, mv_keys, mv_out;   // meshvis.hip: uploaded inputs (seven segments of a D2rStage), triangle records, the large-triangle queue, shade bytes, mesh + cube key buffers, rgb + ids of the current call
     Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots (the segments of a D2rStage per entry point), result frames, union-find parents + component statistics of a pass
+    Buf thumb_in, thumb_ws, thumb_out;   // masks.hip, object thumbnails: frames + noise + records (one D2rStage), statistics / labelling / blur workspace, the packed thumbnails
+    D2rThumbPlan thumb_plan;     // ... the records of the last d2r_thumbs_plan
+    D2rStageTimer thumb_timer[2];   // ... upload / kernels / download of the last plan and of the last fill (d2r_thumbs_get_timing adds them)
     D2rStageTimer mask_timer;    // ... upload / kernels / download of the last batch call (d2r_masks_get_timing)
     D2rStageTimer pcdb_timer;    // pcdbuild.hip: upload / kernels of the last d2r_pcd_build (d2r_pcd_build_get_timing)
     Buf lens_tab;                // undistorted camera-space directions of the current view's pixels (nerf.hip lens_table)

@@ -158,12 +158,13 @@ class ImaginationEngine:
     """The reference's ImaginationEngine: build_scene_model, interpret_user_instr, dream_best_pose."""
 
     def __init__(self, cfg: PathConfig, ctx, scorer, *, text_embeds=None, text_encoder=None, tokenizer=None, depths_gt=None,
-                 lang_model=None, segmentor=None, intrinsics=None):
+                 lang_model=None, segmentor=None, intrinsics=None, captioner=None):
         self.cfg, self.ctx, self.scorer = cfg, ctx, scorer
         self.text_embeds, self.text_encoder, self.tokenizer = text_embeds, text_encoder, tokenizer
         self.depths_gt = depths_gt                       # [L, h, w] sensor depth of the render views (dream2real.py:117-118), or None
         self.data_dir = cfg.data_dir
         self.lang_model, self.segmentor = lang_model, segmentor
+        self.captioner = captioner                       # callable(list of uint8 [h,w,3] thumbnails) -> list of captions, or None
         if intrinsics is None:
             from .scene import INTRINSICS_REALSENSE_1280
             intrinsics = INTRINSICS_REALSENSE_1280
@@ -177,7 +178,9 @@ class ImaginationEngine:
 
     def build_scene_model(self, raw_data=None, *, captions=None):
         """reference dream2real.py:101-177.  raw_data: (rgbs uint8 [N,H,W,3], depths [N,H,W] metres, T_WC [N,4,4]), default the
-        frames of data_dir.  captions: one name per object, "__background__" first; default the captions.json of data_dir.
+        frames of data_dir.  captions: one name per object, "__background__" first; default: with captioner= the engine's captioner
+        on the GPU-built thumbnails (caption.caption_objs; captions.json is written, or read under use_cache_captions), else the
+        captions.json of data_dir.
         Sets self.scene_model, self.out_scene_bound_masks and self.depths_gt."""
         import torch
         from . import segmentation
@@ -233,9 +236,17 @@ class ImaginationEngine:
 
         captions_path = os.path.join(self.data_dir, "captions.json")                                              # :83, :162-164
         given = captions is not None
-        if not given:
+        thumbnails = [None] * num_objs
+        if not given and self.captioner is not None:               # :162-164, caption.py:55-169 with the image work on the GPU
+            from . import caption
+            captions, thumbnails = caption.caption_objs(
+                num_objs, rgbs, masks, self.lang_model, self.out_scene_bound_masks, self.topdown, multi_view=cfg.multi_view_captions,
+                single_view_idx=cfg.single_view_idx, ctx=self.ctx, captioner=self.captioner, cache_path=captions_path,
+                read_cache=cfg.use_cache_captions)
+        elif not given:
             if not os.path.exists(captions_path):
-                raise RuntimeError(f"build_scene_model: captioning models are out of scope; pass captions=[...] or provide {captions_path}")
+                raise RuntimeError(f"build_scene_model: captioning models are out of scope; pass captions=[...] or provide {captions_path}, "
+                                   "or pass captioner=callable(list of thumbnails) -> list of captions to the engine")
             with open(captions_path) as f:
                 captions = json.load(f)
         captions = list(captions)
@@ -245,7 +256,6 @@ class ImaginationEngine:
         if given and not cfg.use_cache_captions:                   # the reference's captioner leaves its result there (caption.py:166-167)
             with open(captions_path, "w") as f:
                 json.dump(captions, f)
-        thumbnails = [None] * num_objs
 
         vis_models = [None] * num_objs                             # created lazily once the task is known (:167-168)
         objs = [ObjectModel(captions[k], vis_models[k], phys_models[k], init_poses[k], thumbnails[k], k) for k in range(num_objs)]

@@ -87,3 +87,23 @@ def load_cached_masks(out_dir, n):
     """segment_associate's cache branch: <out_dir>/XMem_masks/rgb_%04d.png for n frames -> uint8 [n,H,W]."""
     mask_dir = os.path.join(out_dir, "XMem_masks")
     return np.stack([_lib.png_read_grey(os.path.join(mask_dir, "rgb_%04d.png" % k), 8) for k in range(n)])
+
+
+def mask_touches_edge(mask) -> bool:
+    """reference segmentation/sam_seg.py:286-297: a boolean mask [h,w] with at least one set pixel has one on the frame's border"""
+    m = _np(mask).astype(bool)
+    rows, cols = np.nonzero(m.any(axis=1))[0], np.nonzero(m.any(axis=0))[0]
+    return bool(rows[0] == 0 or rows[-1] == m.shape[0] - 1 or cols[0] == 0 or cols[-1] == m.shape[1] - 1)
+
+
+def get_thumbnail(img, obj_mask, padding=5, use_mask=True):
+    """reference segmentation/sam_seg.py:250-271: img [h,w,3] white outside obj_mask (with use_mask), cropped to the mask's bounding
+    box widened by `padding` and clamped to the frame.  Host numpy; the engine's thumbnails come from caption.object_thumbnails."""
+    img, m = _np(img), _np(obj_mask).astype(bool)
+    if use_mask:
+        img = img.copy()
+        img[~m] = 255
+    rows, cols = np.nonzero(m.any(axis=1))[0], np.nonzero(m.any(axis=0))[0]
+    first_row, last_row = max(0, rows[0] - padding), min(img.shape[0] - 1, rows[-1] + padding)
+    first_col, last_col = max(0, cols[0] - padding), min(img.shape[1] - 1, cols[-1] + padding)
+    return img[first_row:last_row + 1, first_col:last_col + 1]

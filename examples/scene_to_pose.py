@@ -1,6 +1,7 @@
 """A scan folder and a settings file in, the best pose out: the three calls of ImaginationEngine.
-    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis]
+    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--dump-thumbnails DIR]
 --vis also writes best_pose_vis.png (and, without use_vis_pcds, cost_volume.png) into the folder.
+--dump-thumbnails DIR writes the objects' captioning thumbnails as DIR/obj_<object>_<k>.png, to caption them elsewhere.
 The folder holds poses.txt, images/, depth/, XMem_masks/ (use_cache_segs), captions.json and lang_cache.json (a
 CachedLangModel file); clip_dir holds a CLIP checkpoint: model.safetensors, vocab.json, merges.txt."""
 import os
@@ -12,8 +13,13 @@ from dream2real_amd.clip_model import load_clip_safetensors
 from dream2real_amd.dream2real import CachedLangModel, ImaginationEngine, PathConfig
 from dream2real_amd.tokenizer import ClipBpeTokenizer
 
-vis = "--vis" in sys.argv[1:]
-config_file, data_dir, user_instr, clip_dir = [a for a in sys.argv[1:] if a != "--vis"][:4]
+argv, dump_dir = sys.argv[1:], None
+if "--dump-thumbnails" in argv:
+    at = argv.index("--dump-thumbnails")
+    dump_dir = argv[at + 1]
+    del argv[at:at + 2]
+vis = "--vis" in argv
+config_file, data_dir, user_instr, clip_dir = [a for a in argv if a != "--vis"][:4]
 cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=True, phys_backend="tsdf")
 ctx = engine.Context(0)
 clip_cfg, state = load_clip_safetensors(os.path.join(clip_dir, "model.safetensors"))
@@ -23,6 +29,15 @@ imagination = ImaginationEngine(cfg, ctx, engine.ClipScorer(ctx, clip_cfg, state
                                                                      context_length=clip_cfg["ctx"]),
                                 lang_model=CachedLangModel(os.path.join(data_dir, "lang_cache.json")))
 imagination.build_scene_model()
+if dump_dir is not None:
+    from dream2real_amd import _lib, caption
+    scene = imagination.scene_model
+    os.makedirs(dump_dir, exist_ok=True)
+    thumbnails = caption.object_thumbnails(len(scene.objs), scene.rgbs, scene.masks, imagination.out_scene_bound_masks, imagination.topdown,
+                                           cfg.multi_view_captions, cfg.single_view_idx, ctx=ctx)
+    for obj_idx, obj_thumbnails in enumerate(thumbnails, start=1):
+        for k, image in enumerate(obj_thumbnails):
+            _lib.png_write(image, os.path.join(dump_dir, "obj_%03d_%02d.png" % (obj_idx, k)))
 task_model = imagination.interpret_user_instr(user_instr)
 best_pose, pose_batch, pose_scores = imagination.dream_best_pose(task_model, vis_cost_vol=vis)
 print(best_pose)

@@ -839,6 +839,45 @@ D2R_API int d2r_masks_census(d2r_ctx *ctx, const uint8_t *masks_u8, uint32_t n, 
  * upload, kernels, download, in milliseconds. */
 D2R_API int d2r_masks_get_timing(d2r_ctx *ctx, double *ms_out);
 
+/* ------------------------------------------------- object thumbnails for captioning
+ *
+ * replaces the image work of reference caption.py:62-130 (Captioner.caption_objs: per object and frame a mask against the scene
+ * bounds, its area, bounding box and border contact, the container test of frame 0, for containers a 201 x 201 Gaussian blur,
+ * a dilation and noise, the crop).  The rule is DESIGN.md section 2g.  Count, then fill: d2r_thumbs_plan uploads the frames,
+ * runs the statistics and the container test and applies the acceptance rule; d2r_thumbs_fill writes every accepted thumbnail
+ * into one packed buffer.  The frames stay on the device in between; another plan replaces them.
+ */
+#define D2R_THUMB_REC_WORDS 10u       /* object, frame, flags, area, row0, col0, rows, cols, offset low, offset high */
+#define D2R_THUMB_ACCEPTED 1u         /* flags: the record has a thumbnail of rows x cols x 3 bytes at its offset */
+#define D2R_THUMB_CONTAINER 2u        /*        the object is a container (decided on frame 0) */
+#define D2R_THUMB_ROTATED 4u          /*        the frame is rotated counter-clockwise by 90 degrees; the crop is in the rotated frame */
+#define D2R_THUMB_EDGE 8u             /*        the object touches the frame's border */
+#define D2R_THUMB_SMALL 16u           /*        area < min_area */
+#define D2R_THUMB_PARAM_WORDS 7u      /* topdown, multi_view, single_view_idx, min_area, hole_area, pad, dilate_k */
+
+/* rgbs host [n][h][w][3], masks_u8 host [n][h][w] labels (0 the background object), oob_u8 host [n][h][w] (non-zero: outside
+ * the scene); params host [D2R_THUMB_PARAM_WORDS] (the reference: min_area 200, hole_area 400, pad 5, dilate_k 60).  One record
+ * per (object 1 .. num_objs - 1, visited frame), objects outermost, frames increasing: (num_objs - 1) * (multi_view ? n : 1) of
+ * them.  *n_recs: the capacity of recs_out in records on entry (ignored when recs_out is NULL), the count on return; recs_out
+ * host [n_recs][D2R_THUMB_REC_WORDS], NULL = run, keep the plan, return the counts only.  *total_bytes: the size of the packed
+ * buffer d2r_thumbs_fill writes; a record's offset is a multiple of 4.  Refused with D2R_ERR_INVALID: num_objs 0 or > 255,
+ * dilate_k outside 1 .. 64, single_view_idx >= n (without multi_view), a capacity below the count. */
+D2R_API int d2r_thumbs_plan(d2r_ctx *ctx, const uint8_t *rgbs, const uint8_t *masks_u8, const uint8_t *oob_u8, uint32_t n, uint32_t w,
+                            uint32_t h, uint32_t num_objs, const uint32_t *params, uint32_t *recs_out, uint32_t *n_recs,
+                            uint64_t *total_bytes);
+
+/* noise_u8 host [h][w][3]; out_u8 host [total_bytes], at least the plan's total.  Runs blur and dilation for the accepted
+ * container records, then one launch composes every accepted thumbnail.  Refused: no plan on this context, total_bytes too small. */
+D2R_API int d2r_thumbs_fill(d2r_ctx *ctx, const uint8_t *noise_u8, uint8_t *out_u8, uint64_t total_bytes);
+
+/* Parity hook on one image: bits_u8 host [h][w] (non-zero = 1) -> out_u8 host [h][w] 0 / 1, the blur bit of section 2g dilated
+ * by dilate_k x dilate_k (1 .. 64; 1 = the blur bit itself). */
+D2R_API int d2r_thumbs_blur_bits(d2r_ctx *ctx, const uint8_t *bits_u8, uint32_t w, uint32_t h, uint32_t dilate_k, uint8_t *out_u8);
+
+/* Device-event times of the context's last d2r_thumbs_plan plus its last d2r_thumbs_fill: ms_out host [3] = upload, kernels,
+ * download, in milliseconds. */
+D2R_API int d2r_thumbs_get_timing(d2r_ctx *ctx, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif
