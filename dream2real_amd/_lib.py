@@ -102,6 +102,8 @@ PROTOTYPES = {
     "d2r_thumbs_fill": (_int, (_ptr, _ptr, _ptr, _u64)),
     "d2r_thumbs_blur_bits": (_int, (_ptr, _ptr, _u32, _u32, _u32, _ptr)),
     "d2r_thumbs_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_proposals_labels": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr)),
+    "d2r_proposals_get_timing": (_int, (_ptr, _ptr)),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -488,6 +490,33 @@ def thumbs_blur_bits(ctx, bits, dilate_k: int = 60) -> np.ndarray:
     out = np.empty(b.shape, np.uint8)
     check(load().d2r_thumbs_blur_bits(_h(ctx), ptr(b), b.shape[1], b.shape[0], dilate_k, ptr(out)), _h(ctx))
     return out
+
+
+PROP_REC_WORDS = 8                                      # D2R_PROP_REC_WORDS: area, ncomp, stage, label, boundary, ew, eh, dd
+PROP_MAX = 1024                                         # D2R_PROP_MAX
+
+
+def proposals_labels(ctx, props, inside=None, records: bool = False, inter: bool = False):
+    """d2r_proposals_labels: proposals uint8 [m,h,w] (non-zero = set), inside uint8 [h,w] or None -> the label
+    image uint8 [h,w]; with records / inter also uint32 [m, PROP_REC_WORDS] / uint32 [m,m] (a tuple in that order)."""
+    p = np.ascontiguousarray(props, np.uint8)
+    assert p.ndim == 3
+    m, h, w = p.shape
+    s = None if inside is None else np.ascontiguousarray(inside, np.uint8)
+    assert s is None or s.shape == (h, w)
+    labels = np.zeros((h, w), np.uint8)
+    recs = np.zeros((m, PROP_REC_WORDS), np.uint32) if records else None
+    mat = np.zeros((m, m), np.uint32) if inter else None
+    check(load().d2r_proposals_labels(_h(ctx), ptr(p), ptr(s), m, w, h, ptr(labels), ptr(recs), ptr(mat)), _h(ctx))
+    out = (labels,) + ((recs,) if records else ()) + ((mat,) if inter else ())
+    return out if len(out) > 1 else labels
+
+
+def proposals_timing(ctx):
+    """d2r_proposals_get_timing -> (upload, kernels, download) of the context's last proposals_labels, device-event milliseconds."""
+    ms = np.zeros(3, np.float64)
+    check(load().d2r_proposals_get_timing(_h(ctx), ptr(ms)), _h(ctx))
+    return tuple(float(x) for x in ms)
 
 
 def thumbs_timing(ctx):

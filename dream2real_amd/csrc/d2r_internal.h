@@ -142,6 +142,8 @@ struct d2r_ctx {
     Buf thumb_in, thumb_ws, thumb_out;   // masks.hip, object thumbnails: frames + noise + records (one D2rStage), statistics / labelling / blur workspace, the packed thumbnails
     D2rThumbPlan thumb_plan;     // ... the records of the last d2r_thumbs_plan
     D2rStageTimer thumb_timer[2];   // ... upload / kernels / download of the last plan and of the last fill (d2r_thumbs_get_timing adds them)
+    Buf prop_in, prop_ws, prop_out;   // proposals.hip: the uploaded proposals + scene mask, the packed planes / union-find parents / records / pair matrix (one D2rStage), the label image
+    D2rStageTimer prop_timer;    // ... upload / kernels / download of the last d2r_proposals_labels (d2r_proposals_get_timing)
     D2rStageTimer mask_timer;    // ... upload / kernels / download of the last batch call (d2r_masks_get_timing)
     D2rStageTimer pcdb_timer;    // pcdbuild.hip: upload / kernels of the last d2r_pcd_build (d2r_pcd_build_get_timing)
     Buf lens_tab;                // undistorted camera-space directions of the current view's pixels (nerf.hip lens_table)

@@ -3,7 +3,7 @@
 // (reference segmentation/XMem_infer.py:264-351, one cv2.connectedComponents per label per frame).  The rule is DESIGN.md
 // section 2d, restated in numpy by tests/masks_ref.py and held to it bit for bit.
 //   k_scene_bounds   one lane per pixel in fp64, the raw mask bit-packed: 64 pixels per uint64 through __ballot
-//   k_morph          dilation / erosion by a k x k rectangle on the packed words: log2(k) shift-and-OR (AND) steps along a row,
+//   k_morph          (masks_shared.h) dilation / erosion by a k x k rectangle on the packed words: log2(k) shift-and-OR (AND) steps along a row,
 //                    the same doubling over the rows of an LDS tile of words
 //   k_label_tiles    union-find over raster indices inside a 64 x 16 tile in LDS
 //   k_label_seams    unions across tile borders, lock-free: find both roots, atomicMin the larger root's parent
@@ -32,13 +32,10 @@
 #include <vector>
 
 #include "d2r_internal.h"
+#include "masks_shared.h"
 
 namespace {
 
-constexpr uint32_t MK_THREADS = 256;
-constexpr int CL_TW = 4, CL_TR = 64, CL_ROWS = 128;      // k_morph: words x output rows of a tile, rows held (CL_TR + 63 <= CL_ROWS)
-constexpr int LB_TW = 64, LB_TH = 16, LB_PX = LB_TW * LB_TH;   // k_label_tiles: tile of the per-tile labelling
-constexpr uint32_t NO_KEY = 0xffffffffu;
 constexpr uint32_t CS_ITERS = 8, CS_SEGS = MK_THREADS * CS_ITERS;   // k_census: 16-byte segments per lane, per workgroup (32 KiB of pixels)
 constexpr size_t MK_WS_BUDGET = (size_t)1 << 30;         // labelling workspace per pass of frames (D2R_MASKS_WS_BYTES overrides it)
 
@@ -78,81 +75,6 @@ __global__ __launch_bounds__(MK_THREADS) void k_scene_bounds(const uint16_t *__r
     if (lane == 0) bits[(size_t)f * H * WW + word] = m;
 }
 
-// x (192 bits, x[0] lowest) >>= s with `fill` shifted in at the top, 1 <= s <= 63
-__device__ inline void shr192(const unsigned long long x[3], int s, unsigned long long fill, unsigned long long y[3])
-{
-    y[0] = (x[0] >> s) | (x[1] << (64 - s));
-    y[1] = (x[1] >> s) | (x[2] << (64 - s));
-    y[2] = (x[2] >> s) | (fill << (64 - s));
-}
-
-// dst(i, j) = OR (ERODE: AND) of src(i + a, j + b), a and b in [-k/2, -k/2 + k - 1], positions outside the frame ignored (they read
-// as the operation's identity, the tail bits of a row's last word included).  A workgroup makes CL_TW words x CL_TR rows.
-template <bool ERODE>
-__global__ __launch_bounds__(MK_THREADS) void k_morph(const unsigned long long *__restrict__ src, unsigned long long *__restrict__ dst, int W, int H,
-                                                      int WW, int k)
-{
-    __shared__ unsigned long long buf[2][CL_ROWS][CL_TW];
-    const unsigned long long ident = ERODE ? ~0ull : 0ull;
-    const int t = (int)threadIdx.x, hh = k / 2;
-    const int w0 = (int)blockIdx.x * CL_TW, i0 = (int)blockIdx.y * CL_TR;
-    const unsigned long long *s = src + (size_t)blockIdx.z * H * WW;
-    unsigned long long *o = dst + (size_t)blockIdx.z * H * WW;
-    const unsigned long long tail = (W & 63) ? (~0ull << (W & 63)) : 0ull;      // the bits past the row's end in its last word
-    auto ld = [&](int gi, int w) -> unsigned long long {
-        if (gi < 0 || gi >= H || w < 0 || w >= WW) return ident;
-        unsigned long long v = s[(size_t)gi * WW + w];
-        if (w == WW - 1) v = ERODE ? (v | tail) : (v & ~tail);
-        return v;
-    };
-    auto op = [](unsigned long long a, unsigned long long b) -> unsigned long long { return ERODE ? (a & b) : (a | b); };
-    for (int q = t; q < CL_ROWS * CL_TW; q += (int)MK_THREADS) {
-        const int r = q / CL_TW, cw = q - r * CL_TW, gi = i0 - hh + r, w = w0 + cw;
-        unsigned long long v = ident;
-        if (r < CL_TR + k - 1 && w < WW && gi >= 0 && gi < H) {
-            unsigned long long x[3] = {ld(gi, w - 1), ld(gi, w), ld(gi, w + 1)}, y[3];
-            // x(j) = op over src(j .. j + L - 1), L doubling up to k
-            int L = 1;
-            while (2 * L <= k) {
-                shr192(x, L, ident, y);
-                x[0] = op(x[0], y[0]); x[1] = op(x[1], y[1]); x[2] = op(x[2], y[2]);
-                L *= 2;
-            }
-            if (k > L) {
-                shr192(x, k - L, ident, y);
-                x[0] = op(x[0], y[0]); x[1] = op(x[1], y[1]); x[2] = op(x[2], y[2]);
-            }
-            v = hh ? ((x[1] << hh) | (x[0] >> (64 - hh))) : x[1];       // the window starts k/2 to the left
-        }
-        buf[0][r][cw] = v;
-    }
-    __syncthreads();
-    int cur = 0;
-    auto step = [&](int sft) {
-        for (int q = t; q < CL_ROWS * CL_TW; q += (int)MK_THREADS) {
-            const int r = q / CL_TW, cw = q - r * CL_TW;
-            const unsigned long long a = buf[cur][r][cw], bb = r + sft < CL_ROWS ? buf[cur][r + sft][cw] : ident;
-            buf[cur ^ 1][r][cw] = op(a, bb);
-        }
-        __syncthreads();
-        cur ^= 1;
-    };
-    int L = 1;
-    while (2 * L <= k) {
-        step(L);
-        L *= 2;
-    }
-    if (k > L) step(k - L);
-    for (int q = t; q < CL_TR * CL_TW; q += (int)MK_THREADS) {
-        const int r = q / CL_TW, cw = q - r * CL_TW, gi = i0 + r, w = w0 + cw;
-        if (gi < H && w < WW) {
-            unsigned long long v = buf[cur][r][cw];       // tile row r = frame row gi - k/2: the window's first row
-            if (w == WW - 1) v &= ~tail;
-            o[(size_t)gi * WW + w] = v;
-        }
-    }
-}
-
 // packed bits -> 0 / 255 bytes, eight pixels per lane
 __global__ __launch_bounds__(MK_THREADS) void k_unpack(const unsigned long long *__restrict__ bits, int W, int H, int WW, uint8_t *__restrict__ out)
 {
@@ -174,36 +96,6 @@ __global__ __launch_bounds__(MK_THREADS) void k_unpack(const unsigned long long 
 }
 
 // ------------------------------------------------------------------------------------------------ labelling
-
-// Union-find where a link always goes from the larger index to the smaller: a root is the smallest index of its set whatever
-// order the atomics ran in.  `par` is LDS or global memory that other lanes update with atomicMin while it is read.
-template <int SCOPE>
-__device__ inline uint32_t uf_find(uint32_t *par, uint32_t x)
-{
-    for (;;) {
-        const uint32_t p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, SCOPE);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-template <int SCOPE>
-__device__ inline void uf_unite(uint32_t *par, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = uf_find<SCOPE>(par, a);
-        b = uf_find<SCOPE>(par, b);
-        if (a == b) return;
-        if (a < b) {
-            const uint32_t s = a;
-            a = b;
-            b = s;
-        }
-        const uint32_t old = atomicMin(&par[a], b);       // a was a root: linked; else a's parent `old` < a still has to meet b
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // parent[g] = raster index of the smallest pixel of g's component INSIDE its tile (label 0: g itself)
 __global__ __launch_bounds__(MK_THREADS) void k_label_tiles(const uint8_t *__restrict__ mask, int W, int H, uint32_t *__restrict__ parent)

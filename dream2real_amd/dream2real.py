@@ -4,7 +4,8 @@
 `dream_best_pose` (physics pre-filter, renderer, `optimise_pose_grid`, the three text files), in the reference's order and
 with its switches.  `PathConfig.from_json` reads the reference's settings files.
 
-The models the reference downloads enter from outside: segmentation (SAM, XMem) as a `segmentor(rgbs, depths)` callable or
+The models the reference downloads enter from outside: segmentation as a `proposer` (SAM's mask generator alone) and a
+`tracker` (XMem alone) with the first label image built between them on the GPU, or as a `segmentor(rgbs, depths)` callable, or
 the XMem_masks cache, captioning as a `captions` list or the captions.json cache, the LLM as a `lang_model` object (any
 object with `parse_instr`, `get_movable_obj_idx`, `get_relevant_obj_idxs`; `CachedLangModel` answers from a JSON file), CLIP
 as `scorer` (+ text embeddings, or a text encoder and tokenizer).  NeRF training still raises: camera poses come from
@@ -158,13 +159,19 @@ class ImaginationEngine:
     """The reference's ImaginationEngine: build_scene_model, interpret_user_instr, dream_best_pose."""
 
     def __init__(self, cfg: PathConfig, ctx, scorer, *, text_embeds=None, text_encoder=None, tokenizer=None, depths_gt=None,
-                 lang_model=None, segmentor=None, intrinsics=None, captioner=None):
+                 lang_model=None, segmentor=None, intrinsics=None, captioner=None, proposer=None, tracker=None):
         self.cfg, self.ctx, self.scorer = cfg, ctx, scorer
         self.text_embeds, self.text_encoder, self.tokenizer = text_embeds, text_encoder, tokenizer
         self.depths_gt = depths_gt                       # [L, h, w] sensor depth of the render views (dream2real.py:117-118), or None
         self.data_dir = cfg.data_dir
         self.lang_model, self.segmentor = lang_model, segmentor
         self.captioner = captioner                       # callable(list of uint8 [h,w,3] thumbnails) -> list of captions, or None
+        if (proposer is None) != (tracker is None):
+            raise ValueError("ImaginationEngine: proposer= and tracker= come together, " +
+                             ("tracker=" if tracker is None else "proposer=") + " is missing")
+        # proposer: callable(uint8 [W,H,3], frame 0 turned upright) -> bool [M,W,H] mask proposals (SAM's mask generator alone);
+        # tracker: callable(rgbs, labels0 uint8 [H,W]) -> uint8 [N,H,W] raw label images (XMem alone)
+        self.proposer, self.tracker = proposer, tracker
         if intrinsics is None:
             from .scene import INTRINSICS_REALSENSE_1280
             intrinsics = INTRINSICS_REALSENSE_1280
@@ -207,10 +214,23 @@ class ImaginationEngine:
             raw_masks = np.asarray(_np(self.segmentor(rgbs, depths)), np.uint8)
             masks = segmentation.refine_masks(raw_masks, depths, loader.T_WC_data, intrinsics, self.out_scene_bound_masks,
                                               cfg.scene_centre, self.data_dir, ctx=self.ctx)
+        elif self.proposer is not None:
+            # segment_associate with every frame associated (XMem_infer.py:199-236): proposals on the upright first frame, the
+            # rule of DESIGN.md section 2h on the GPU, the tracker over all frames, then the same refinement
+            rgbs_np = _np(rgbs)
+            first = np.rot90(rgbs_np[0], 1)
+            inside = np.rot90(_np(self.out_scene_bound_masks[0]) == 0)
+            labels0 = np.rot90(segmentation.proposals_to_labels(self.proposer(first), inside, ctx=self.ctx), 3)
+            raw_masks = np.asarray(_np(self.tracker(rgbs, np.ascontiguousarray(labels0))), np.uint8)
+            if raw_masks.shape != rgbs_np.shape[:3]:
+                raise ValueError(f"tracker returned label images of shape {raw_masks.shape}, expected {rgbs_np.shape[:3]}")
+            masks = segmentation.refine_masks(raw_masks, depths, loader.T_WC_data, intrinsics, self.out_scene_bound_masks,
+                                              cfg.scene_centre, self.data_dir, ctx=self.ctx)
         else:
             raise RuntimeError("build_scene_model: running SAM and XMem is out of scope; either set use_cache_segs and provide "
                                "XMem_masks/rgb_%04d.png in data_dir, or pass segmentor=callable(rgbs, depths) -> uint8 [N,H,W] "
-                               "raw label images to the engine")
+                               "raw label images to the engine, or pass proposer= (image -> mask proposals) and tracker= "
+                               "(frames, first label image -> label images) and let the engine build the first label image")
 
         _, num_objs, self.label_counts = segmentation.label_census(masks, ctx=self.ctx)                           # :139-144
         if num_objs == 0:

@@ -3,8 +3,9 @@ components of a raw label image, the area rule, the component nearest the scene 
 (disconnected_prune), the out-of-scene overwrite, and the XMem_masks/rgb_%04d.png files everything downstream reads.  The rule
 is DESIGN.md section 2d.
 
-Running SAM or XMem is out of scope: whatever produced the raw label images (XMem in the reference), `refine_masks` is the
-body of the `segment_associate` loop from there on and `load_cached_masks` its cache branch."""
+Running SAM or XMem is out of scope: `proposals_to_labels` turns the mask generator's proposals into the first frame's label
+image (sam_seg.py:80-115 and integrate_masks); whatever produced the raw label images of all frames (XMem in
+the reference), `refine_masks` is the body of the `segment_associate` loop from there on and `load_cached_masks` its cache branch."""
 from __future__ import annotations
 
 import os
@@ -14,6 +15,7 @@ import numpy as np
 from . import _lib
 
 MIN_COMPONENT_AREA = 200          # XMem_infer.py:289, :340
+PROPOSAL_RECORD = np.dtype([(k, np.uint32) for k in ("area", "ncomp", "stage", "label", "boundary", "ew", "eh", "dd")])
 
 
 def _np(x):
@@ -57,6 +59,32 @@ def refine_masks(raw_masks, depths, T_WC, intrinsics, out_scene_bound_masks, sce
         for k in range(refined.shape[0]):
             _lib.png_write_channels(refined[k], os.path.join(mask_dir, "rgb_%04d.png" % k))
     return refined
+
+
+def proposals_to_labels(proposals, inside=None, *, ctx, return_records=False):
+    """The reference's Segmentor.segment after the mask generator (segmentation/sam_seg.py:80-115) and integrate_masks
+    (XMem_infer.py:256-261) in one GPU call: proposals bool [M,H,W] in the proposer's order, inside bool [H,W] (True inside the
+    scene bounds) or None -> the label image uint8 [H,W], survivors numbered 1, 2, ... in proposal order, the highest label on top.
+    The rule is DESIGN.md section 2h.  With return_records also one record per proposal: area, ncomp, stage (0 kept, 1 disconnected,
+    2 large, 3 subpart, 4 small), label, boundary, ew, eh, dd."""
+    p = _np(proposals)
+    if p.ndim != 3:
+        raise ValueError(f"proposals must be [M, H, W], got shape {p.shape}")
+    if p.shape[0] > _lib.PROP_MAX:
+        raise ValueError(f"at most {_lib.PROP_MAX} proposals per call, got {p.shape[0]}")
+    if p.shape[1] == 0 or p.shape[2] == 0:
+        raise ValueError(f"proposals must have a height and a width, got shape {p.shape}")
+    s = None
+    if inside is not None:
+        s = _np(inside)
+        if s.shape != p.shape[1:]:
+            raise ValueError(f"inside must be [H, W] = {tuple(p.shape[1:])}, got shape {s.shape}")
+        s = (s != 0).astype(np.uint8)
+    out = _lib.proposals_labels(ctx, (p != 0).astype(np.uint8), s, records=return_records)
+    if not return_records:
+        return out
+    labels, recs = out
+    return labels, np.ascontiguousarray(recs).view(PROPOSAL_RECORD).reshape(-1)
 
 
 def labels_from_census(counts):

@@ -1,7 +1,10 @@
 """A scan folder and a settings file in, the best pose out: the three calls of ImaginationEngine.
-    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--dump-thumbnails DIR]
+    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy]
 --vis also writes best_pose_vis.png (and, without use_vis_pcds, cost_volume.png) into the folder.
 --dump-thumbnails DIR writes the objects' captioning thumbnails as DIR/obj_<object>_<k>.png, to caption them elsewhere.
+--proposals FILE.npy --tracked FILE.npy stand in for the two segmentation models: the mask generator's recorded proposals, bool [M,W,H]
+for the first frame turned upright, and the tracker's recorded raw label images, uint8 [N,H,W]; the engine builds the first label image
+between them instead of reading XMem_masks/.
 The folder holds poses.txt, images/, depth/, XMem_masks/ (use_cache_segs), captions.json and lang_cache.json (a
 CachedLangModel file); clip_dir holds a CLIP checkpoint: model.safetensors, vocab.json, merges.txt."""
 import os
@@ -18,16 +21,28 @@ if "--dump-thumbnails" in argv:
     at = argv.index("--dump-thumbnails")
     dump_dir = argv[at + 1]
     del argv[at:at + 2]
+recorded = {}
+for flag in ("--proposals", "--tracked"):
+    if flag in argv:
+        at = argv.index(flag)
+        recorded[flag] = argv[at + 1]
+        del argv[at:at + 2]
+if len(recorded) == 1:
+    sys.exit("--proposals and --tracked come together")
 vis = "--vis" in argv
 config_file, data_dir, user_instr, clip_dir = [a for a in argv if a != "--vis"][:4]
-cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=True, phys_backend="tsdf")
+cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=not recorded, phys_backend="tsdf")
+models = {}
+if recorded:
+    import numpy as np
+    models = dict(proposer=lambda image: np.load(recorded["--proposals"]), tracker=lambda frames, labels0: np.load(recorded["--tracked"]))
 ctx = engine.Context(0)
 clip_cfg, state = load_clip_safetensors(os.path.join(clip_dir, "model.safetensors"))
 imagination = ImaginationEngine(cfg, ctx, engine.ClipScorer(ctx, clip_cfg, state),
                                 text_encoder=engine.TextEncoder(ctx, clip_cfg, state),
                                 tokenizer=ClipBpeTokenizer.from_files(os.path.join(clip_dir, "vocab.json"), os.path.join(clip_dir, "merges.txt"),
                                                                      context_length=clip_cfg["ctx"]),
-                                lang_model=CachedLangModel(os.path.join(data_dir, "lang_cache.json")))
+                                lang_model=CachedLangModel(os.path.join(data_dir, "lang_cache.json")), **models)
 imagination.build_scene_model()
 if dump_dir is not None:
     from dream2real_amd import _lib, caption

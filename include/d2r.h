@@ -878,6 +878,32 @@ D2R_API int d2r_thumbs_blur_bits(d2r_ctx *ctx, const uint8_t *bits_u8, uint32_t 
  * download, in milliseconds. */
 D2R_API int d2r_thumbs_get_timing(d2r_ctx *ctx, double *ms_out);
 
+/* ------------------------------------------------- mask proposals to the first frame's label image
+ *
+ * replaces the post-processing of reference segmentation/sam_seg.py:80-115 (Segmentor.segment after the mask generator: the
+ * scene-bound AND, the disconnected / large / subpart / small rules with cv2.dilate, cv2.connectedComponents, cv2.findContours
+ * and cv2.minAreaRect per mask on the CPU) and integrate_masks (segmentation/XMem_infer.py:256-261).  The rule is DESIGN.md
+ * section 2h: integer arithmetic only, the result does not depend on the order the threads ran in.
+ */
+#define D2R_PROP_REC_WORDS 8u         /* area, components of the 5 x 5 dilation, dropping stage (0 kept, 1 disconnected, 2 large,
+                                       * 3 subpart, 4 small), label, boundary pixels of the chosen component, ew, eh, dd */
+#define D2R_PROP_MAX 1024u            /* proposals per call */
+#define D2R_PROP_MAX_SIDE 8192u       /* width and height */
+
+/* props_u8 host [m][h][w] (non-zero = set) in the proposer's order, inside_u8 (optional) host [h][w] (non-zero = inside the
+ * scene bounds); labels_out host [h][w]: 0, or the label 1, 2, ... of the last surviving proposal that covers the pixel.
+ * recs_out (optional) host [m][D2R_PROP_REC_WORDS]: every field is filled for every proposal, whatever stage dropped it.
+ * inter_out (optional) host [m][m]: |P[i] & P[j]| for i < j among the proposals that passed stages 1 and 2, 0 elsewhere.
+ * m = 0 gives an all-zero image.  Refused with D2R_ERR_INVALID and labels_out, recs_out, inter_out untouched: m above
+ * D2R_PROP_MAX, a zero width or height or one above D2R_PROP_MAX_SIDE, more than 255 survivors; D2R_ERR_UNSUPPORTED: m * w * h
+ * of 2^32 or more. */
+D2R_API int d2r_proposals_labels(d2r_ctx *ctx, const uint8_t *props_u8, const uint8_t *inside_u8, uint32_t m, uint32_t w, uint32_t h,
+                                 uint8_t *labels_out, uint32_t *recs_out, uint32_t *inter_out);
+
+/* Device-event times of the context's last d2r_proposals_labels with m > 0: ms_out host [3] = upload, kernels, download, in
+ * milliseconds. */
+D2R_API int d2r_proposals_get_timing(d2r_ctx *ctx, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif
