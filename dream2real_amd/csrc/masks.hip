@@ -5,10 +5,11 @@
 //   k_scene_bounds   one lane per pixel in fp64, the raw mask bit-packed: 64 pixels per uint64 through __ballot
 //   k_morph          (masks_shared.h) dilation / erosion by a k x k rectangle on the packed words: log2(k) shift-and-OR (AND) steps along a row,
 //                    the same doubling over the rows of an LDS tile of words
-//   k_label_tiles    union-find over raster indices inside a 64 x 16 tile in LDS
+//   k_label_tiles    (masks_shared.h, over ByteSrc, as the next two) union-find over raster indices inside a 64 x 16 tile in LDS
 //   k_label_seams    unions across tile borders, lock-free: find both roots, atomicMin the larger root's parent
 //   k_label_flatten  every pixel points at its root = the smallest raster index of its component = the component's order key
 //   k_comp_stats     area and (n, sum d, sum j d, sum i d) at the root's index: integer atomics, equal roots combined per wave
+//                    (wave_each_root, masks_shared.h)
 //   k_select_*       per label: component count, best distance (bit pattern of a non-negative double) or area, tie rule
 //   k_prune_write    the pruned label image with the out-of-scene overwrite
 //   k_mask_lut       out = lut[mask] | (oob != 0), optionally alpha = 255 (1 - out)
@@ -23,6 +24,8 @@
 //   k_thumb_blur_rows / k_thumb_blur_cols   the separable 201-tap integer blur: bits -> u16 row sums -> the blur bit, packed again, in
 //                    the rotated frame's layout where the frame is rotated; k_morph<false> dilates it
 //   k_thumb_compose  every accepted thumbnail into one packed buffer: rotation, white or noise fill, crop
+// The one-wave-per-word kernels (k_scene_bounds, k_thumb_pack) index and pack through d2r_word_lane / word_pack, single bits are read
+// through plane_bit, the frames of a pass come from pass_items: all in masks_shared.h.
 // Every value is written by ordinary vector stores from C++.
 #include <math.h>
 #include <stdlib.h>
@@ -57,9 +60,9 @@ __global__ __launch_bounds__(MK_THREADS) void k_scene_bounds(const uint16_t *__r
                                                              int W, int H, int WW, unsigned long long *__restrict__ bits)
 {
     const uint32_t f = blockIdx.y;
-    const uint32_t word = blockIdx.x * (MK_THREADS / 64) + (threadIdx.x >> 6);      // one wave per word of 64 pixels
-    if (word >= (uint32_t)H * (uint32_t)WW) return;
-    const int i = (int)(word / (uint32_t)WW), w = (int)(word - (uint32_t)i * (uint32_t)WW), lane = (int)(threadIdx.x & 63), j = w * 64 + lane;
+    WordLane p;
+    if (!d2r_word_lane(H, WW, p)) return;
+    const int i = p.i, j = p.j;
     bool set = false;
     if (j < W) {
         const uint16_t d = depth[(size_t)f * W * H + (size_t)i * W + j];
@@ -71,8 +74,7 @@ __global__ __launch_bounds__(MK_THREADS) void k_scene_bounds(const uint16_t *__r
         const double pz = (((double)T[8] * x + (double)T[9] * y) + (double)T[10] * z) + (double)T[11];
         set = d > 0 && pz > -0.40 && (px < b.lo[0] || px > b.hi[0] || py < b.lo[1] || py > b.hi[1] || pz < b.lo[2] || pz > b.hi[2]);
     }
-    const unsigned long long m = __ballot(set);
-    if (lane == 0) bits[(size_t)f * H * WW + word] = m;
+    word_pack(p, set, bits + (size_t)f * H * WW);
 }
 
 // packed bits -> 0 / 255 bytes, eight pixels per lane
@@ -97,78 +99,6 @@ __global__ __launch_bounds__(MK_THREADS) void k_unpack(const unsigned long long 
 
 // ------------------------------------------------------------------------------------------------ labelling
 
-// parent[g] = raster index of the smallest pixel of g's component INSIDE its tile (label 0: g itself)
-__global__ __launch_bounds__(MK_THREADS) void k_label_tiles(const uint8_t *__restrict__ mask, int W, int H, uint32_t *__restrict__ parent)
-{
-    __shared__ uint8_t lab[LB_PX];
-    __shared__ uint32_t par[LB_PX];
-    const int t = (int)threadIdx.x, j0 = (int)blockIdx.x * LB_TW, i0 = (int)blockIdx.y * LB_TH;
-    const size_t base = (size_t)blockIdx.z * W * H;
-    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
-        const int r = q / LB_TW, c = q - r * LB_TW, i = i0 + r, j = j0 + c;
-        lab[q] = (i < H && j < W) ? mask[base + (size_t)i * W + j] : 0;
-        par[q] = (uint32_t)q;
-    }
-    __syncthreads();
-    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
-        const int r = q / LB_TW, c = q - r * LB_TW;
-        const uint8_t l = lab[q];
-        if (!l) continue;
-        if (c > 0 && lab[q - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - 1));
-        if (r > 0) {
-            if (c > 0 && lab[q - LB_TW - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW - 1));
-            if (lab[q - LB_TW] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW));
-            if (c + 1 < LB_TW && lab[q - LB_TW + 1] == l) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW + 1));
-        }
-    }
-    __syncthreads();
-    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
-        const int r = q / LB_TW, c = q - r * LB_TW, i = i0 + r, j = j0 + c;
-        if (i >= H || j >= W) continue;
-        const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q);
-        const int rr = (int)root / LB_TW, rc = (int)root - rr * LB_TW;
-        parent[base + (size_t)i * W + j] = (uint32_t)(i0 + rr) * (uint32_t)W + (uint32_t)(j0 + rc);
-    }
-}
-
-// pixels on a tile border meet their W / NW / N / NE neighbours of equal label in the neighbouring tiles
-__global__ __launch_bounds__(MK_THREADS) void k_label_seams(const uint8_t *__restrict__ mask, int W, int H, uint32_t *__restrict__ parent)
-{
-    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
-    if (g >= (uint32_t)W * (uint32_t)H) return;
-    const int i = (int)(g / (uint32_t)W), j = (int)(g - (uint32_t)i * (uint32_t)W);
-    const bool top = (i % LB_TH) == 0, left = (j % LB_TW) == 0, right = (j % LB_TW) == LB_TW - 1;
-    if (!(top || left || right)) return;
-    const uint8_t *m = mask + (size_t)blockIdx.y * W * H;
-    uint32_t *par = parent + (size_t)blockIdx.y * W * H;
-    const uint8_t l = m[g];
-    if (!l) return;
-    if (left && j > 0 && m[g - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - 1);
-    if (i > 0) {
-        if ((top || left) && j > 0 && m[g - W - 1] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W - 1);
-        if (top && m[g - W] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W);
-        if ((top || right) && j + 1 < W && m[g - W + 1] == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W + 1);
-    }
-}
-
-// parent[g] = root; a root's statistics start at zero.  Writes race only with reads that accept any ancestor.
-__global__ __launch_bounds__(MK_THREADS) void k_label_flatten(const uint8_t *__restrict__ mask, int W, int H, uint32_t *__restrict__ parent,
-                                                              unsigned long long *__restrict__ stats)
-{
-    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
-    if (g >= (uint32_t)W * (uint32_t)H) return;
-    const size_t base = (size_t)blockIdx.y * W * H;
-    if (!mask[base + g]) return;
-    uint32_t *par = parent + base;
-    const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, g);
-    if (root != g) {
-        par[g] = root;
-    } else {
-        unsigned long long *st = stats + (base + g) * ST_WORDS;
-        for (int e = 0; e < ST_WORDS; ++e) st[e] = 0ull;
-    }
-}
-
 __device__ inline unsigned long long wave_sum(unsigned long long v)
 {
     for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
@@ -182,7 +112,6 @@ __global__ __launch_bounds__(MK_THREADS) void k_comp_stats(const uint8_t *__rest
 {
     const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
     const size_t base = (size_t)blockIdx.y * W * H;
-    const int lane = (int)(threadIdx.x & 63);
     bool active = false;
     uint32_t root = NO_KEY;
     unsigned long long d = 0, jd = 0, id = 0;
@@ -194,16 +123,11 @@ __global__ __launch_bounds__(MK_THREADS) void k_comp_stats(const uint8_t *__rest
         jd = (unsigned long long)j * d;
         id = (unsigned long long)i * d;
     }
-    unsigned long long todo = __ballot(active);
-    while (todo) {                                          // wave-uniform: one turn per distinct root among the 64 pixels
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t r0 = __shfl(root, leader);
+    wave_each_root(active, root, [&](uint32_t r0, unsigned long long members, bool leader) {
         const bool mine = active && root == r0;
-        const unsigned long long members = __ballot(mine);
-        const unsigned long long area = (unsigned long long)__popcll(members);
         const unsigned long long n = (unsigned long long)__popcll(__ballot(mine && d > 0));
         const unsigned long long sd = wave_sum(mine ? d : 0ull), sjd = wave_sum(mine ? jd : 0ull), sid = wave_sum(mine ? id : 0ull);
-        if (lane == leader) {
+        if (leader) {
             unsigned long long *st = stats + (base + r0) * ST_WORDS;
             if (n) {
                 atomicAdd(&st[0], n);
@@ -211,10 +135,9 @@ __global__ __launch_bounds__(MK_THREADS) void k_comp_stats(const uint8_t *__rest
                 atomicAdd(&st[2], sjd);
                 atomicAdd(&st[3], sid);
             }
-            atomicAdd(reinterpret_cast<uint32_t *>(&st[4]), (uint32_t)area);
+            atomicAdd(reinterpret_cast<uint32_t *>(&st[4]), (uint32_t)__popcll(members));
         }
-        todo &= ~members;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ selection
@@ -483,7 +406,6 @@ __global__ __launch_bounds__(MK_THREADS) void k_thumb_comp_stats(const uint8_t *
 {
     const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
     const size_t base = (size_t)blockIdx.y * W * H;
-    const int lane = (int)(threadIdx.x & 63);
     bool active = false, zero = false, border = false;
     uint32_t root = NO_KEY;
     if (g < (uint32_t)W * (uint32_t)H && comp[base + g]) {
@@ -493,20 +415,15 @@ __global__ __launch_bounds__(MK_THREADS) void k_thumb_comp_stats(const uint8_t *
         const uint32_t i = g / (uint32_t)W, j = g - i * (uint32_t)W;
         border = i == 0 || j == 0 || i == (uint32_t)H - 1u || j == (uint32_t)W - 1u;
     }
-    unsigned long long todo = __ballot(active);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t r0 = __shfl(root, leader);
+    wave_each_root(active, root, [&](uint32_t r0, unsigned long long, bool leader) {
         const bool mine = active && root == r0;
-        const unsigned long long members = __ballot(mine);
         const unsigned long long nz = (unsigned long long)__popcll(__ballot(mine && zero)), nb = (unsigned long long)__popcll(__ballot(mine && border));
-        if (lane == leader) {
+        if (leader) {
             unsigned long long *st = stats + (base + r0) * ST_WORDS;
             if (nz) atomicAdd(&st[0], nz);
             if (nb) atomicAdd(&st[1], nb);
         }
-        todo &= ~members;
-    }
+    });
 }
 
 // one thread per root: area >= hole_area, 10 |comp & label 0| <= 7 area, no pixel on the border -> the object is a container
@@ -527,20 +444,18 @@ __global__ __launch_bounds__(MK_THREADS) void k_thumb_container(const uint8_t *_
 __global__ __launch_bounds__(MK_THREADS) void k_thumb_pack(const uint8_t *__restrict__ mask, const uint8_t *__restrict__ oob,
                                                            const ThumbRec *__restrict__ recs, int W, int H, int WW, unsigned long long *__restrict__ bits)
 {
-    const uint32_t word = blockIdx.x * (MK_THREADS / 64) + (threadIdx.x >> 6);
-    if (word >= (uint32_t)H * (uint32_t)WW) return;
-    const int i = (int)(word / (uint32_t)WW), w = (int)(word - (uint32_t)i * (uint32_t)WW), lane = (int)(threadIdx.x & 63), j = w * 64 + lane;
+    WordLane p;
+    if (!d2r_word_lane(H, WW, p)) return;
     bool set = false;
-    if (j < W) {
+    if (p.j < W) {
         if (recs) {
-            const size_t g = (size_t)recs[blockIdx.y].frame * W * H + (size_t)i * W + j;
+            const size_t g = (size_t)recs[blockIdx.y].frame * W * H + (size_t)p.i * W + p.j;
             set = !(mask[g] == recs[blockIdx.y].obj && oob[g] == 0);
         } else {
-            set = mask[(size_t)i * W + j] != 0;
+            set = mask[(size_t)p.i * W + p.j] != 0;
         }
     }
-    const unsigned long long m = __ballot(set);
-    if (lane == 0) bits[(size_t)blockIdx.y * H * WW + word] = m;
+    word_pack(p, set, bits + (size_t)blockIdx.y * H * WW);
 }
 
 // rowv(i, x) = sum_t q[t] b(i, reflect(x + t)): TH_RS pixels of one row per workgroup, their bits and the halo unpacked into LDS
@@ -550,10 +465,7 @@ __global__ __launch_bounds__(MK_THREADS) void k_thumb_blur_rows(const unsigned l
     __shared__ uint8_t seg[TH_RS + 2 * TH_R];
     const int t = (int)threadIdx.x, x0 = (int)blockIdx.x * TH_RS, i = (int)blockIdx.y;
     const unsigned long long *row = bits + (size_t)blockIdx.z * H * WW + (size_t)i * WW;
-    for (int q = t; q < TH_RS + 2 * TH_R; q += (int)MK_THREADS) {
-        const int m = thumb_reflect(x0 - TH_R + q, W);
-        seg[q] = (uint8_t)((row[m >> 6] >> (m & 63)) & 1ull);
-    }
+    for (int q = t; q < TH_RS + 2 * TH_R; q += (int)MK_THREADS) seg[q] = plane_bit(row, WW, 0, thumb_reflect(x0 - TH_R + q, W));
     __syncthreads();
     const int x = x0 + t;
     if (x >= W) return;
@@ -623,8 +535,7 @@ __global__ __launch_bounds__(MK_THREADS) void k_thumb_compose(const uint8_t *__r
             const uint8_t *src = rgb + fat * 3;
             bool white = false;
             if (container) {
-                const unsigned long long word = bits[rec.bits_off + (size_t)ri * (rot ? HW : WW) + (rj >> 6)];
-                if ((word >> (rj & 63)) & 1ull) src = noise + at * 3;
+                if (plane_bit(bits + rec.bits_off, rot ? HW : WW, (int)ri, (int)rj)) src = noise + at * 3;
             } else {
                 white = !(mask[fat] == rec.obj && oob[fat] == 0);
             }
@@ -665,26 +576,15 @@ int masks_check_frames(d2r_ctx *ctx, uint32_t n, uint32_t w, uint32_t h)
 void masks_label(d2r_ctx *ctx, const uint8_t *mask, const uint16_t *depth, uint32_t nf, uint32_t w, uint32_t h, uint32_t *parent,
                  unsigned long long *stats)
 {
-    const uint32_t px = w * h, gpx = (px + MK_THREADS - 1) / MK_THREADS;
-    hipLaunchKernelGGL(k_label_tiles, dim3((w + LB_TW - 1) / LB_TW, (h + LB_TH - 1) / LB_TH, nf), dim3(MK_THREADS), 0, ctx->stream, mask, (int)w,
-                       (int)h, parent);
-    hipLaunchKernelGGL(k_label_seams, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, mask, (int)w, (int)h, parent);
-    hipLaunchKernelGGL(k_label_flatten, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, mask, (int)w, (int)h, parent, stats);
-    hipLaunchKernelGGL(k_comp_stats, dim3(gpx, nf), dim3(MK_THREADS), 0, ctx->stream, mask, depth, (int)w, (int)h, (const uint32_t *)parent, stats);
+    label_components(ctx, ByteSrc{mask, (int)w, (int)h}, nf, parent, stats, 8 * ST_WORDS);
+    hipLaunchKernelGGL(k_comp_stats, dim3((w * h + MK_THREADS - 1) / MK_THREADS, nf), dim3(MK_THREADS), 0, ctx->stream, mask, depth, (int)w, (int)h,
+                       (const uint32_t *)parent, stats);
 }
 
-// frames per pass of d2r_masks_prune.  D2R_MASKS_WS_BYTES lowers (or raises) the workspace budget, so that a test can drive a small
-// batch through several passes, the way 100 frames of 1280 x 720 go with the default (26 frames per pass).
+// frames per pass of d2r_masks_prune: 100 frames of 1280 x 720 go 26 per pass with the default budget
 uint32_t masks_pass_frames(uint32_t n, size_t px)
 {
-    size_t budget = MK_WS_BUDGET;
-    if (const char *v = getenv("D2R_MASKS_WS_BYTES")) {
-        char *end = nullptr;
-        const unsigned long long b = strtoull(v, &end, 10);
-        if (end != v && *end == 0 && b > 0) budget = (size_t)b;
-    }
-    const size_t per = px * (4 + 8 * ST_WORDS);
-    return (uint32_t)std::max<size_t>(1, std::min<size_t>(n, budget / per));
+    return pass_items("D2R_MASKS_WS_BYTES", MK_WS_BUDGET, n, px * (4 + 8 * ST_WORDS));
 }
 
 // blur bit of `slots` packed images (b0, rows of ww words) dilated by k x k into `dil`.  recs null: the images' own frame, one slot.

@@ -4,10 +4,11 @@
 // tests/proposals_ref.py and held to it bit for bit.  Integer arithmetic only; every sum, maximum and flag is order-free.
 //   k_prop_pack         M proposals -> rows of 64-bit words, AND with the scene mask, the area's popcount: one read of the bytes
 //   k_morph<false>      (masks_shared.h) the 5 x 5 dilation of every plane of a pass
-//   k_prop_label_tiles  union-find inside a 64 x 16 tile (one word per row) straight from the bits
-//   k_prop_label_seams  unions across tile borders
-//   k_prop_roots        COUNT: components of a plane = its roots; else parent[g] = root, a root's boundary counter starts at zero
+//   k_label_tiles / k_label_seams / k_label_flatten   (masks_shared.h) the labeller of masks.hip over BitSrc: a 64 x 16 tile is one
+//                       word of 16 rows, straight from the bits; a root's boundary counter starts at zero
+//   k_prop_roots        components of a dilated plane = its roots after tiles and seams
 //   k_prop_boundary     boundary pixels (a set pixel with an unset 4-neighbour; outside the image reads unset) counted at their root
+//                       (wave_each_root, masks_shared.h)
 //   k_prop_best         the component with the most boundary pixels, ties to the lowest first pixel: one 64-bit atomicMax
 //   k_prop_geometry     one workgroup per mask: the chosen component's leftmost / rightmost pixel per row, a monotone chain over them
 //                       (serial), every hull edge's extents across the lanes, the smallest rectangle by an exact 128-bit compare
@@ -16,7 +17,6 @@
 //   k_prop_select       stages 3 and 4, the labels, the records (one workgroup: M^2 flag logic)
 //   k_prop_compose      the label image: the highest label whose mask covers the pixel
 // Every value is written by ordinary vector stores from C++.
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -32,137 +32,55 @@ constexpr int PR_CHUNK = 128;                             // ... words of a mask
 constexpr uint32_t PR_NONE = 0xffffffffu;
 constexpr int GEO_WORDS = 4;                              // per mask: boundary pixels of the chosen component, ew, eh, dd
 
-__device__ inline bool plane_bit(const unsigned long long *__restrict__ bits, int WW, int i, int j)
-{
-    return (bits[(size_t)i * WW + (j >> 6)] >> (j & 63)) & 1ull;
-}
-
 // one wave per word of 64 pixels of proposal blockIdx.y; area[m] += the word's popcount
 __global__ __launch_bounds__(MK_THREADS) void k_prop_pack(const uint8_t *__restrict__ props, const uint8_t *__restrict__ inside, int W, int H, int WW,
                                                           unsigned long long *__restrict__ bits, uint32_t *__restrict__ area)
 {
-    const uint32_t word = blockIdx.x * (MK_THREADS / 64) + (threadIdx.x >> 6);
-    if (word >= (uint32_t)H * (uint32_t)WW) return;
-    const int i = (int)(word / (uint32_t)WW), w = (int)(word - (uint32_t)i * (uint32_t)WW), lane = (int)(threadIdx.x & 63), j = w * 64 + lane;
+    WordLane p;
+    if (!d2r_word_lane(H, WW, p)) return;
     bool set = false;
-    if (j < W) {
-        const size_t at = (size_t)i * W + j;
+    if (p.j < W) {
+        const size_t at = (size_t)p.i * W + p.j;
         set = props[(size_t)blockIdx.y * W * H + at] != 0 && (!inside || inside[at] != 0);
     }
-    const unsigned long long m = __ballot(set);
-    if (lane == 0) {
-        bits[(size_t)blockIdx.y * H * WW + word] = m;
-        if (m) atomicAdd(&area[blockIdx.y], (uint32_t)__popcll(m));
-    }
+    const unsigned long long m = word_pack(p, set, bits + (size_t)blockIdx.y * H * WW);
+    if (p.lane == 0 && m) atomicAdd(&area[blockIdx.y], (uint32_t)__popcll(m));
 }
 
-// parent[g] = raster index of the smallest pixel of g's component INSIDE its tile, for the set pixels (unset ones are left alone:
-// every reader tests the bit first).  The tile is word blockIdx.x of LB_TH rows.
-__global__ __launch_bounds__(MK_THREADS) void k_prop_label_tiles(const unsigned long long *__restrict__ bits, int W, int H, int WW,
-                                                                 uint32_t *__restrict__ parent)
-{
-    __shared__ unsigned long long row[LB_TH];
-    __shared__ uint32_t par[LB_PX];
-    const int t = (int)threadIdx.x, j0 = (int)blockIdx.x * LB_TW, i0 = (int)blockIdx.y * LB_TH;
-    const unsigned long long *b = bits + (size_t)blockIdx.z * H * WW;
-    if (t < LB_TH) row[t] = i0 + t < H ? b[(size_t)(i0 + t) * WW + blockIdx.x] : 0ull;      // the tail bits of a row's last word are 0
-    for (int q = t; q < LB_PX; q += (int)MK_THREADS) par[q] = (uint32_t)q;
-    __syncthreads();
-    auto bit = [&](int r, int c) -> bool { return (row[r] >> c) & 1ull; };
-    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
-        const int r = q / LB_TW, c = q - r * LB_TW;
-        if (!bit(r, c)) continue;
-        if (c > 0 && bit(r, c - 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - 1));
-        if (r > 0) {
-            if (c > 0 && bit(r - 1, c - 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW - 1));
-            if (bit(r - 1, c)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW));
-            if (c + 1 < LB_TW && bit(r - 1, c + 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW + 1));
-        }
-    }
-    __syncthreads();
-    uint32_t *out = parent + (size_t)blockIdx.z * W * H;
-    for (int q = t; q < LB_PX; q += (int)MK_THREADS) {
-        const int r = q / LB_TW, c = q - r * LB_TW;
-        if (!bit(r, c)) continue;                       // a set bit lies inside the image
-        const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q);
-        const int rr = (int)root / LB_TW, rc = (int)root - rr * LB_TW;
-        out[(size_t)(i0 + r) * W + j0 + c] = (uint32_t)(i0 + rr) * (uint32_t)W + (uint32_t)(j0 + rc);
-    }
-}
-
-// set pixels on a tile border meet their set W / NW / N / NE neighbours in the neighbouring tiles
-__global__ __launch_bounds__(MK_THREADS) void k_prop_label_seams(const unsigned long long *__restrict__ bits, int W, int H, int WW,
-                                                                 uint32_t *__restrict__ parent)
-{
-    const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
-    if (g >= (uint32_t)W * (uint32_t)H) return;
-    const int i = (int)(g / (uint32_t)W), j = (int)(g - (uint32_t)i * (uint32_t)W);
-    const bool top = (i % LB_TH) == 0, left = (j % LB_TW) == 0, right = (j % LB_TW) == LB_TW - 1;
-    if (!(top || left || right)) return;
-    const unsigned long long *b = bits + (size_t)blockIdx.y * H * WW;
-    uint32_t *par = parent + (size_t)blockIdx.y * W * H;
-    if (!plane_bit(b, WW, i, j)) return;
-    if (left && j > 0 && plane_bit(b, WW, i, j - 1)) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - 1);
-    if (i > 0) {
-        if ((top || left) && j > 0 && plane_bit(b, WW, i - 1, j - 1)) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W - 1);
-        if (top && plane_bit(b, WW, i - 1, j)) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W);
-        if ((top || right) && j + 1 < W && plane_bit(b, WW, i - 1, j + 1)) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W + 1);
-    }
-}
-
-// COUNT: ncomp[mask] += the plane's roots (a wave's roots in one add).  Else parent[g] = root and a root's boundary counter
-// starts at zero; those writes race only with reads that accept any ancestor.
-template <bool COUNT>
+// ncomp[mask] += the plane's roots after k_label_tiles and k_label_seams (a wave's roots in one add)
 __global__ __launch_bounds__(MK_THREADS) void k_prop_roots(const unsigned long long *__restrict__ bits, int W, int H, int WW,
-                                                           uint32_t *__restrict__ parent, uint32_t *__restrict__ ncomp, uint32_t *__restrict__ bcnt)
+                                                           uint32_t *__restrict__ parent, uint32_t *__restrict__ ncomp)
 {
     const uint32_t g = blockIdx.x * MK_THREADS + threadIdx.x;
-    const size_t base = (size_t)blockIdx.y * W * H;
     bool is_root = false;
     if (g < (uint32_t)W * (uint32_t)H) {
         const int i = (int)(g / (uint32_t)W), j = (int)(g - (uint32_t)i * (uint32_t)W);
-        if (plane_bit(bits + (size_t)blockIdx.y * H * WW, WW, i, j)) {
-            uint32_t *par = parent + base;
-            if (COUNT) {
-                is_root = __hip_atomic_load(&par[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g;
-            } else {
-                const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, g);
-                if (root != g) par[g] = root;
-                else bcnt[base + g] = 0;
-            }
-        }
+        if (plane_bit(bits + (size_t)blockIdx.y * H * WW, WW, i, j))
+            is_root = __hip_atomic_load(&parent[(size_t)blockIdx.y * W * H + g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g;
     }
-    if (COUNT) {
-        const unsigned long long roots = __ballot(is_root);
-        if (roots && (threadIdx.x & 63) == 0) atomicAdd(&ncomp[blockIdx.y], (uint32_t)__popcll(roots));
-    }
+    const unsigned long long roots = __ballot(is_root);
+    if (roots && (threadIdx.x & 63) == 0) atomicAdd(&ncomp[blockIdx.y], (uint32_t)__popcll(roots));
 }
 
 // one wave per word: the word's boundary bits from its four neighbours, counted at the pixels' roots (equal roots of a wave in one add)
 __global__ __launch_bounds__(MK_THREADS) void k_prop_boundary(const unsigned long long *__restrict__ bits, int W, int H, int WW,
                                                               const uint32_t *__restrict__ parent, uint32_t *__restrict__ bcnt)
 {
-    const uint32_t word = blockIdx.x * (MK_THREADS / 64) + (threadIdx.x >> 6);
-    if (word >= (uint32_t)H * (uint32_t)WW) return;
-    const int i = (int)(word / (uint32_t)WW), w = (int)(word - (uint32_t)i * (uint32_t)WW), lane = (int)(threadIdx.x & 63);
+    WordLane p;
+    if (!d2r_word_lane(H, WW, p)) return;
     const unsigned long long *b = bits + (size_t)blockIdx.y * H * WW;
-    const unsigned long long v = b[word];
+    const unsigned long long v = b[p.word];
     if (!v) return;                                         // wave-uniform
-    const unsigned long long up = i > 0 ? b[word - WW] : 0ull, down = i + 1 < H ? b[word + WW] : 0ull;
-    const unsigned long long prev = w > 0 ? b[word - 1] : 0ull, next = w + 1 < WW ? b[word + 1] : 0ull;
+    const unsigned long long up = p.i > 0 ? b[p.word - WW] : 0ull, down = p.i + 1 < H ? b[p.word + WW] : 0ull;
+    const unsigned long long prev = p.w > 0 ? b[p.word - 1] : 0ull, next = p.w + 1 < WW ? b[p.word + 1] : 0ull;
     const unsigned long long lft = (v << 1) | (prev >> 63), rgt = (v >> 1) | (next << 63);      // bit j = the pixel at j - 1, at j + 1
     const unsigned long long edge = v & ~(up & down & lft & rgt);
     const size_t base = (size_t)blockIdx.y * W * H;
-    const bool active = (edge >> lane) & 1ull;
-    const uint32_t root = active ? parent[base + (size_t)i * W + w * 64 + lane] : PR_NONE;
-    unsigned long long todo = edge;
-    while (todo) {                                          // wave-uniform: one turn per distinct root among the boundary pixels
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t r0 = __shfl(root, leader);
-        const unsigned long long members = __ballot(active && root == r0);
-        if (lane == leader) atomicAdd(&bcnt[base + r0], (uint32_t)__popcll(members));
-        todo &= ~members;
-    }
+    const bool active = (edge >> p.lane) & 1ull;
+    const uint32_t root = active ? parent[base + (size_t)p.i * W + p.j] : PR_NONE;
+    wave_each_root(active, root, [&](uint32_t r0, unsigned long long members, bool leader) {
+        if (leader) atomicAdd(&bcnt[base + r0], (uint32_t)__popcll(members));
+    });
 }
 
 // best[mask] = max over its components of (boundary pixels << 32 | ~first pixel): the most boundary pixels, then the lowest raster index
@@ -433,33 +351,19 @@ __global__ __launch_bounds__(MK_THREADS) void k_prop_compose(const unsigned long
                                                              const uint32_t *__restrict__ lab2mask, const uint32_t *__restrict__ status,
                                                              uint8_t *__restrict__ out)
 {
-    const uint32_t word = blockIdx.x * (MK_THREADS / 64) + (threadIdx.x >> 6);
-    if (word >= (uint32_t)H * (uint32_t)WW) return;
+    WordLane p;
+    if (!d2r_word_lane(H, WW, p)) return;
     const uint32_t n = status[0];
     if (n > 255u) return;                                   // the call fails; nothing is read back
-    const int i = (int)(word / (uint32_t)WW), w = (int)(word - (uint32_t)i * (uint32_t)WW), lane = (int)(threadIdx.x & 63), j = w * 64 + lane;
     const size_t words = (size_t)H * WW;
-    unsigned long long open = (W - w * 64) >= 64 ? ~0ull : ((1ull << (W - w * 64)) - 1ull);      // pixels of the word without a label yet
+    unsigned long long open = (W - p.w * 64) >= 64 ? ~0ull : ((1ull << (W - p.w * 64)) - 1ull);      // pixels of the word without a label yet
     uint32_t label = 0;
     for (uint32_t l = n; l > 0 && open; --l) {
-        const unsigned long long v = bits[(size_t)lab2mask[l - 1] * words + word] & open;
-        if ((v >> lane) & 1ull) label = l;
+        const unsigned long long v = bits[(size_t)lab2mask[l - 1] * words + p.word] & open;
+        if ((v >> p.lane) & 1ull) label = l;
         open &= ~v;
     }
-    if (j < W) out[(size_t)i * W + j] = (uint8_t)label;
-}
-
-// masks per pass of the labelling: a pixel costs a parent and a boundary counter, a word its dilated plane
-uint32_t props_pass_masks(uint32_t m, size_t px, size_t words, uint32_t h)
-{
-    size_t budget = PR_WS_BUDGET;
-    if (const char *v = getenv("D2R_PROPOSALS_WS_BYTES")) {
-        char *end = nullptr;
-        const unsigned long long b = strtoull(v, &end, 10);
-        if (end != v && *end == 0 && b > 0) budget = (size_t)b;
-    }
-    const size_t per = px * 8 + words * 8 + ((size_t)h * 5 + 2) * 4;
-    return (uint32_t)std::max<size_t>(1, std::min<size_t>(m, budget / per));
+    if (p.j < W) out[(size_t)p.i * W + p.j] = (uint8_t)label;
 }
 
 }  // namespace
@@ -482,7 +386,8 @@ int d2r_proposals_labels(d2r_ctx *ctx, const uint8_t *props_u8, const uint8_t *i
     }
     D2R_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ww = (w + 63) / 64, words = (size_t)h * ww;
-    const uint32_t per = props_pass_masks(m, px, words, h);
+    // masks per pass of the labelling: a pixel costs a parent and a boundary counter, a word its dilated plane
+    const uint32_t per = pass_items("D2R_PROPOSALS_WS_BYTES", PR_WS_BUDGET, m, px * 8 + words * 8 + ((size_t)h * 5 + 2) * 4);
     D2rStage in(ctx, ctx->prop_in), ws(ctx, ctx->prop_ws);
     const size_t o_props = in.add((size_t)m * px), o_inside = in.add(inside_u8 ? px : 0);
     // the first four segments are cleared together: area, ncomp, best, inter
@@ -509,18 +414,13 @@ int d2r_proposals_labels(d2r_ctx *ctx, const uint8_t *props_u8, const uint8_t *i
     D2R_HIP(ctx, hipMemsetAsync(ws.at<char>(o_area), 0, clear_end - o_area, ctx->stream));
     hipLaunchKernelGGL(k_prop_pack, dim3(gw, m), T, 0, ctx->stream, in.at<const uint8_t>(o_props),
                        inside_u8 ? in.at<const uint8_t>(o_inside) : (const uint8_t *)nullptr, W, H, WW, d_bits, d_area);
-    const dim3 g_tiles((uint32_t)ww, (h + LB_TH - 1) / LB_TH, 1);
     for (uint32_t m0 = 0; m0 < m; m0 += per) {              // passes share the workspace; nothing waits in between
         const uint32_t nm = std::min(per, m - m0);
         const unsigned long long *raw = d_bits + (size_t)m0 * words;
         hipLaunchKernelGGL(k_morph<false>, dim3((uint32_t)((ww + CL_TW - 1) / CL_TW), (h + CL_TR - 1) / CL_TR, nm), T, 0, ctx->stream, raw, d_dil, W, H, WW, 5);
-        hipLaunchKernelGGL(k_prop_label_tiles, dim3(g_tiles.x, g_tiles.y, nm), T, 0, ctx->stream, (const unsigned long long *)d_dil, W, H, WW, d_parent);
-        hipLaunchKernelGGL(k_prop_label_seams, dim3(gpx, nm), T, 0, ctx->stream, (const unsigned long long *)d_dil, W, H, WW, d_parent);
-        hipLaunchKernelGGL(k_prop_roots<true>, dim3(gpx, nm), T, 0, ctx->stream, (const unsigned long long *)d_dil, W, H, WW, d_parent, d_ncomp + m0,
-                           (uint32_t *)nullptr);
-        hipLaunchKernelGGL(k_prop_label_tiles, dim3(g_tiles.x, g_tiles.y, nm), T, 0, ctx->stream, raw, W, H, WW, d_parent);
-        hipLaunchKernelGGL(k_prop_label_seams, dim3(gpx, nm), T, 0, ctx->stream, raw, W, H, WW, d_parent);
-        hipLaunchKernelGGL(k_prop_roots<false>, dim3(gpx, nm), T, 0, ctx->stream, raw, W, H, WW, d_parent, (uint32_t *)nullptr, d_bcnt);
+        label_unite(ctx, BitSrc{d_dil, W, H, WW}, nm, d_parent);
+        hipLaunchKernelGGL(k_prop_roots, dim3(gpx, nm), T, 0, ctx->stream, (const unsigned long long *)d_dil, W, H, WW, d_parent, d_ncomp + m0);
+        label_components(ctx, BitSrc{raw, W, H, WW}, nm, d_parent, d_bcnt, 4);
         hipLaunchKernelGGL(k_prop_boundary, dim3(gw, nm), T, 0, ctx->stream, raw, W, H, WW, (const uint32_t *)d_parent, d_bcnt);
         hipLaunchKernelGGL(k_prop_best, dim3(gpx, nm), T, 0, ctx->stream, raw, W, H, WW, (const uint32_t *)d_parent, (const uint32_t *)d_bcnt, d_best + m0);
         hipLaunchKernelGGL(k_prop_geometry, dim3(nm), T, 0, ctx->stream, raw, W, H, WW, (const uint32_t *)d_parent, (const unsigned long long *)(d_best + m0),

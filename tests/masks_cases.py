@@ -74,9 +74,10 @@ def checkerboard(h=33, w=70):
 def arms(h=50, w=130):
     """Two arms of one label that meet only in the last row and the last column."""
     m = np.zeros((h, w), np.uint8)
-    m[:, 3] = 1              # the left arm
+    left = min(3, w - 1)
+    m[:, left] = 1           # the left arm (column 3; the last column of a frame narrower than that)
     m[:, w - 1] = 1          # the right arm: the last column
-    m[h - 1, 3:] = 1         # the last row joins them
+    m[h - 1, left:] = 1      # the last row joins them
     return m
 
 

@@ -229,3 +229,20 @@ def all_cases():
     for m, w, h, seed in PAIR_CASES:
         cases[f"pairs_{m}_{w}x{h}"] = random_blobs(m, w, h, seed)
     return cases
+
+
+# the smallest frames (w, h) at which a tile-staging or seam mistake of the shared labeller shows: exactly one 64 x 16 tile, one
+# pixel into the next tile on both axes, one short of a tile, three tiles by three, and the degenerate frames
+LABELLER_SIZES = ((64, 16), (65, 17), (63, 15), (129, 33), (1, 1), (1, 70), (70, 1))
+
+
+def labeller_images(w, h):
+    """name -> 0 / 1 image [h, w]: the component cases of tests/masks_cases.py and a random image at density 0.5"""
+    from tests import masks_cases
+    rng = np.random.default_rng(1000 * w + h)
+    return {
+        "serpentine": masks_cases.serpentine(h, w),
+        "checkerboard": (masks_cases.checkerboard(h, w) == 1).astype(np.uint8),
+        "arms": masks_cases.arms(h, w),
+        "random": (rng.random((h, w)) < 0.5).astype(np.uint8),
+    }

@@ -113,3 +113,19 @@ def test_refusals_return_invalid_and_leave_the_label_image_alone(ctx):
     assert lib.d2r_proposals_get_timing(ctx.h, None) == -1
     assert np.array_equal(_lib.proposals_labels(ctx, p), np.zeros((4, 4), np.uint8))          # two full masks: both large; the context still works
     assert lib.d2r_proposals_get_timing(ctx.h, _lib.ptr(ms)) == 0 and (ms >= 0).all()
+
+
+@pytest.mark.parametrize("w,h", pc.LABELLER_SIZES)
+def test_both_sources_of_the_labeller_count_the_same_components(ctx, w, h):
+    """One image through both instantiations of k_label_*: the bit-plane source counts the components of the 5 x 5 dilation inside
+    d2r_proposals_labels (record word 1), the byte source labels the same dilation through d2r_masks_components, where a root is a
+    pixel whose key is its own raster index.  Both equal the flood fill's count."""
+    from tests import masks_ref
+    for name, B in pc.labeller_images(w, h).items():
+        D = masks_ref.dilate(B, 5, fast=True)
+        want = int((masks_ref.components(D).ravel() == np.arange(h * w)).sum())
+        _, recs = _lib.proposals_labels(ctx, B[None], records=True)
+        keys, _, _ = _lib.masks_components(ctx, D, np.zeros((h, w), np.uint16))
+        roots = int((keys.ravel() == np.arange(h * w)).sum())
+        print(name, w, h, "bits", int(recs[0, 1]), "bytes", roots, "flood fill", want)
+        assert int(recs[0, 1]) == roots == want, (name, w, h)

@@ -154,3 +154,18 @@ def test_one_callable_without_the_other_is_refused(tmp_path):
         ImaginationEngine(cfg, None, None, proposer=lambda image: None)
     with pytest.raises(ValueError, match="proposer= is missing"):
         ImaginationEngine(cfg, None, None, tracker=lambda frames, labels0: None)
+
+
+@pytest.mark.parametrize("w,h", pc.LABELLER_SIZES)
+def test_the_two_numpy_component_counts_agree_on_the_labeller_cases(w, h):
+    """The flood fill of masks_ref and the minimum propagation proposals_ref counts with: one number per image, both sources of the
+    GPU cross-check (test_proposals_gpu.py) are held to it."""
+    from tests import masks_ref
+    for name, B in pc.labeller_images(w, h).items():
+        assert B.shape == (h, w) and B.dtype == np.uint8 and B.max() <= 1, name
+        D = masks_ref.dilate(B, 5, fast=True)
+        flood = masks_ref.components(D)
+        fast = masks_ref.components_fast(D)
+        n_flood = int((flood.ravel() == np.arange(h * w)).sum())
+        assert n_flood == len(np.unique(fast[D != 0])), (name, w, h)
+        assert (flood == fast).all(), (name, w, h)
