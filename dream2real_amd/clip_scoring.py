@@ -168,12 +168,16 @@ def optimise_pose_grid(renderer, depths_gt, render_cam_pose_idx, task_model, dat
         if physics_only:
             best = int(torch.randint(valid_idxs.shape[0], (1,)).item())
             return torch.from_numpy(valid_poses[best].reshape(4, 4).copy()), torch.from_numpy(pose_batch), torch.ones(N)
-    if not use_cache_renders and use_vis_pcds:
+    # a renderer with world_poses = True (tsdf_visual_model.TsdfRenderer) takes the ablation's route whatever use_vis_pcds says
+    world_poses = getattr(renderer, "world_poses", False)
+    if not use_cache_renders and (use_vis_pcds or world_poses):
         # reference :129-131: view 0 only, its OpenCV pose unconverted, the world-frame candidate poses; no cb_render files
-        if not getattr(renderer, "point_cloud", False):
+        if not world_poses and not getattr(renderer, "point_cloud", False):
             raise NotImplementedError("use_vis_pcds=True needs a pcd_visual_model.PointCloudRenderer (or a renderer with "
                                       "its render(render_pose, pose_batch, task_model) surface and point_cloud = True)")
         if shard is not None or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            if world_poses:
+                raise NotImplementedError("pose sharding of the colour-TSDF visual backend (vis_backend=\"tsdf\") is not implemented")
             raise NotImplementedError("pose sharding of the point-cloud ablation (use_vis_pcds) is not implemented")
         render_poses = get_virtual_cam_poses(task_model, render_cam_pose_idx)
         te, n_goal = text_embeddings()

@@ -137,6 +137,11 @@ struct d2r_ctx {
     // background of the current view
     Buf bg_rgba, bg_depth, bg_u8;
     Buf pcd_mats, pcd_bg_keys, pcd_bg_frame, pcd_cols;   // pcd.hip: candidate matrices, background key buffer and colour frame, colour table of the current call
+    Buf tv_mats, tv_bg_frame, tv_bg_depth, tv_depth;   // tsdfvis.hip: candidate matrices + frame rectangles, the background's ray-cast frame and depth image, the candidates' depth images (parity hook)
+    D2rStageTimer tv_timer, tv_pass_timer;   // ... upload / background cast of the last call, and one pass's candidate cast; tv_cast_ms sums the passes (d2r_tsdfvis_get_timing)
+    D2rStageTimer tv_dl_timer;   // ... one pass's copy of frames and depths to the host (parity hook); tv_dl_ms sums the passes
+    double tv_cast_ms = 0.0, tv_dl_ms = 0.0;
+    bool tv_pass_pending = false, tv_dl_pending = false;
     Buf mv_in, mv_recs, mv_queue, mv_shade, mv_keys, mv_out;   // meshvis.hip: uploaded inputs (seven segments of a D2rStage), triangle records, the large-triangle queue, shade bytes, mesh + cube key buffers, rgb + ids of the current call
     Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots (the segments of a D2rStage per entry point), result frames, union-find parents + component statistics of a pass
     Buf thumb_in, thumb_ws, thumb_out;   // masks.hip, object thumbnails: frames + noise + records (one D2rStage), statistics / labelling / blur workspace, the packed thumbnails
@@ -246,6 +251,21 @@ struct PerDeviceOnce {
     template <class F>
     void run(int device, F &&fn) { std::call_once(flag[device % D2R_MAX_DEVICES], fn); }
 };
+
+// tsdf.hip: a volume as the ray caster (tsdfvis.hip) reads it.  box: the voxels (global coordinates, inclusive) of the blocks any
+// frame touched, lo > hi when there is none; every voxel outside it has weight 0.
+struct D2rTsdfDev {
+    const float2 *vox;           // [nz][ny][nx] (tsdf, weight)
+    const float *col;            // [nz][ny][nx][3], nullptr for a volume without colour
+    const uint8_t *ever;         // [nbz][nby][nbx] non-zero: some frame touched the block
+    int32_t lo[3];               // global coordinate of voxel 0 per axis
+    uint32_t nv[3], nb[3];
+    int32_t box_lo[3], box_hi[3];
+    float voxel;
+};
+bool d2r_tsdf_has_colour(const d2r_tsdf *v);
+int d2r_tsdf_device(const d2r_tsdf *v);
+int d2r_tsdf_dev(d2r_ctx *ctx, d2r_tsdf *v, D2rTsdfDev *out);     // reads the block flags back when frames arrived since the last call (synchronises)
 
 int d2r_pcd_check_view(d2r_ctx *ctx, const d2r_pcd_view *view);      // pcd.hip: the limits d2r_pcd_render holds a view to (meshvis.hip shares them)
 

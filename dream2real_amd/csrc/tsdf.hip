@@ -10,6 +10,8 @@
 //   k_erode        mask eroded by a k x k rectangle (separable minimum over an LDS tile), depth -> metres, invalid -> 0
 //   k_mark_blocks  one lane per valid pixel walks its ray over [z - trunc, z + trunc] in voxel steps and stamps the blocks
 //   k_integrate    one workgroup per block stamped this frame, lanes along x: the running average, frame by frame
+//   k_fuse_rgb     the same body with colour (d2r_tsdf_integrate_rgb): three fp32 channels averaged at
+//                  exactly the voxels the frame updates; k_tsdf_colours gathers them for the parity hook
 //   k_mc_*         classify cubes, mark crossed edges, scan counts in (z, y, x) order, emit vertices, emit triangles
 //   k_tsdf_touch_bits / k_tsdf_solid_*   the volume as the point-against-field physics backend reads it (DESIGN.md section 2e,
 //                  sdfphys.hip): one "touch" bit per voxel, and the centres of the observed solid voxels in (z, y, x) order
@@ -56,9 +58,16 @@ struct d2r_tsdf {
     D2rDev<uint32_t> counters;      // [0] length of list, [1] valid pixels of the frame, [2..3] vertex / triangle totals, [4] solid voxels
     uint32_t frame = 0;
     d2r_ctx::Buf depth_in, mask_in, zbuf;
+    // colour (d2r_tsdf_integrate_rgb): allocated by the first rgb frame
+    D2rDev<float> col;              // [nz][ny][nx][3]
+    enum { FRAMES_NONE, FRAMES_PLAIN, FRAMES_RGB } frames = FRAMES_NONE;   // which of the two calls feeds this volume
+    d2r_ctx::Buf rgb_in;
+    // the touched-block box of d2r_tsdf_dev, as of frame box_frame
+    uint32_t box_frame = 0xffffffffu;
+    int32_t box_lo[3] = {}, box_hi[3] = {};
     ~d2r_tsdf()
     {
-        for (void *p : {depth_in.p, mask_in.p, zbuf.p})
+        for (void *p : {depth_in.p, mask_in.p, zbuf.p, rgb_in.p})
             if (p) (void)hipFree(p);
     }
     // the last extraction, kept for the fill call
@@ -161,9 +170,12 @@ __global__ __launch_bounds__(TSDF_THREADS) void k_mark_blocks(const float *__res
 
 // the running average of one frame over the blocks it stamped.  256 threads = one z-slice of a block: x = t & 15 along the
 // lanes (neighbouring voxels read neighbouring pixels), y = t >> 4; a wave's 64 voxels are four 128-byte rows of state.
-__global__ __launch_bounds__(TSDF_THREADS) void k_integrate(const float *__restrict__ zbuf, TsdfCam c, TsdfGrid G,
-                                                            const uint32_t *__restrict__ list, const uint32_t *__restrict__ counters,
-                                                            float2 *__restrict__ vox)
+// RGB: the voxels whose tsdf is updated also average the pixel's colour, with the weight from before the increment
+// (DESIGN.md section 2i); one launch per frame, so the average is order-exact without atomics.
+template <bool RGB>
+__device__ __forceinline__ void integrate_blocks(const float *__restrict__ zbuf, const TsdfCam &c, const TsdfGrid &G,
+                                                 const uint32_t *__restrict__ list, const uint32_t *__restrict__ counters,
+                                                 float2 *__restrict__ vox, const uint8_t *__restrict__ rgb, float *__restrict__ col)
 {
     const uint32_t n = counters[0];
     const uint32_t x = threadIdx.x & 15u, y = threadIdx.x >> 4;
@@ -190,10 +202,43 @@ __global__ __launch_bounds__(TSDF_THREADS) void k_integrate(const float *__restr
             const float tt = fminf(sdf / G.trunc, 1.0f);
             float2 *s = vox + ((size_t)lz * G.nv[1] + ly) * G.nv[0] + lx;
             float2 sv = *s;
+            if (RGB) {
+                const uint8_t *pix = rgb + ((size_t)(int)v * c.W + (int)u) * 3;
+                float *cv = col + (((size_t)lz * G.nv[1] + ly) * G.nv[0] + lx) * 3;
+                for (int ch = 0; ch < 3; ++ch) cv[ch] = (sv.y * cv[ch] + (float)pix[ch]) / (sv.y + 1.0f);
+            }
             sv.x = (sv.y * sv.x + tt) / (sv.y + 1.0f);
             sv.y = sv.y + 1.0f;
             *s = sv;
         }
+    }
+}
+
+__global__ __launch_bounds__(TSDF_THREADS) void k_integrate(const float *__restrict__ zbuf, TsdfCam c, TsdfGrid G,
+                                                            const uint32_t *__restrict__ list, const uint32_t *__restrict__ counters,
+                                                            float2 *__restrict__ vox)
+{
+    integrate_blocks<false>(zbuf, c, G, list, counters, vox, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(TSDF_THREADS) void k_fuse_rgb(const float *__restrict__ zbuf, const uint8_t *__restrict__ rgb, TsdfCam c, TsdfGrid G,
+                                                           const uint32_t *__restrict__ list, const uint32_t *__restrict__ counters,
+                                                           float2 *__restrict__ vox, float *__restrict__ col)
+{
+    integrate_blocks<true>(zbuf, c, G, list, counters, vox, rgb, col);
+}
+
+// parity hook: the colours of the listed blocks, [n][16][16][16][3] in (z, y, x, channel) order
+__global__ __launch_bounds__(TSDF_THREADS) void k_tsdf_colours(const float *__restrict__ col, TsdfGrid G, const uint32_t *__restrict__ blocks,
+                                                                  float *__restrict__ out)
+{
+    const uint32_t b = blocks[blockIdx.x];
+    const uint32_t bx = b % G.nb[0], by = (b / G.nb[0]) % G.nb[1], bz = b / (G.nb[0] * G.nb[1]);
+    for (uint32_t q = threadIdx.x; q < D2R_TSDF_BLOCK_VOX * 3; q += TSDF_THREADS) {
+        const uint32_t vx = q / 3u, ch = q - vx * 3u;
+        const uint32_t x = vx & 15u, y = (vx >> 4) & 15u, z = vx >> 8;
+        out[(size_t)blockIdx.x * D2R_TSDF_BLOCK_VOX * 3 + q] =
+            col[(((size_t)(bz * D2R_TSDF_BLOCK + z) * G.nv[1] + by * D2R_TSDF_BLOCK + y) * G.nv[0] + bx * D2R_TSDF_BLOCK + x) * 3 + ch];
     }
 }
 
@@ -565,10 +610,10 @@ void d2r_tsdf_destroy(d2r_tsdf *v)
     delete v;
 }
 
-int d2r_tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *mask_u8, uint32_t w, uint32_t h, const float *intrinsics,
-                       const float *cam_pose, uint32_t erode_k)
+// one frame through either call: rgb_u8 == nullptr is d2r_tsdf_integrate
+static int tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *mask_u8, const uint8_t *rgb_u8, uint32_t w, uint32_t h,
+                          const float *intrinsics, const float *cam_pose, uint32_t erode_k)
 {
-    if (!v || !depth_u16 || !mask_u8 || !intrinsics || !cam_pose) return tsdf_fail(v, D2R_ERR_INVALID, "null argument");
     d2r_ctx *ctx = v->ctx;
     if (w == 0 || h == 0 || w > 16384 || h > 16384) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: width and height must be 1 .. 16384");
     if (erode_k < 1 || erode_k > D2R_TSDF_MAX_ERODE) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: erode_k must be 1 .. 32");
@@ -578,7 +623,23 @@ int d2r_tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *ma
         if (!std::isfinite(cam_pose[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: cam_pose must be finite");
     if (intrinsics[0] == 0.f || intrinsics[4] == 0.f) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: focal lengths must not be 0");
     if (v->frame == 0xfffffffeu) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "TSDF volume: too many frames");
+    if (v->frames != d2r_tsdf::FRAMES_NONE && (v->frames == d2r_tsdf::FRAMES_RGB) != (rgb_u8 != nullptr))
+        return d2r_fail(ctx, D2R_ERR_INVALID,
+                        "TSDF volume: a frame through d2r_tsdf_integrate_rgb after d2r_tsdf_integrate (or the other way round) mixes the two "
+                        "calls on one volume; its colours would average over fewer frames than its weights count");
     D2R_HIP(ctx, hipSetDevice(v->device));
+    if (rgb_u8 && !v->col.get()) {
+        if ((double)v->n_vox * 20.0 > (double)D2R_TSDF_MAX_VOXELS * 8.0) {
+            char msg[320];
+            snprintf(msg, sizeof msg,
+                     "TSDF volume over the cap: %u x %u x %u voxels with colour are %.1f GiB of voxel state (20 bytes a voxel); the dense "
+                     "volume is capped at 16 GiB: shrink scene_bounds",
+                     v->G.nv[0], v->G.nv[1], v->G.nv[2], (double)v->n_vox * 20.0 / 1073741824.0);
+            return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, msg);
+        }
+        if (int rc = v->col.alloc(ctx, v->n_vox * 12, TSDF_MEM, true)) return rc;
+    }
+    v->frames = rgb_u8 ? d2r_tsdf::FRAMES_RGB : d2r_tsdf::FRAMES_PLAIN;
     TsdfCam c{};
     c.fx = intrinsics[0];
     c.fy = intrinsics[4];
@@ -593,6 +654,10 @@ int d2r_tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *ma
     const size_t px = (size_t)w * h;
     int rc;
     if ((rc = d2r_reserve(ctx, v->depth_in, px * 2)) || (rc = d2r_reserve(ctx, v->mask_in, px)) || (rc = d2r_reserve(ctx, v->zbuf, px * 4))) return rc;
+    if (rgb_u8) {
+        if ((rc = d2r_reserve(ctx, v->rgb_in, px * 3))) return rc;
+        D2R_HIP(ctx, hipMemcpyAsync(v->rgb_in.p, rgb_u8, px * 3, hipMemcpyHostToDevice, ctx->stream));
+    }
     D2R_HIP(ctx, hipMemcpyAsync(v->depth_in.p, depth_u16, px * 2, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemcpyAsync(v->mask_in.p, mask_u8, px, hipMemcpyHostToDevice, ctx->stream));
     D2R_HIP(ctx, hipMemsetAsync(v->counters.get(), 0, 8, ctx->stream));
@@ -604,10 +669,59 @@ int d2r_tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *ma
     hipLaunchKernelGGL(k_mark_blocks, dim3((uint32_t)((px + TSDF_THREADS - 1) / TSDF_THREADS)), dim3(TSDF_THREADS), 0, ctx->stream,
                        (const float *)v->zbuf.p, c, v->G, steps, cur, v->stamp.get(), v->ever.get(), v->list.get(), v->counters.get());
     const uint32_t grid = std::min<uint32_t>(v->n_blocks, (uint32_t)ctx->n_cu * 16u);
-    hipLaunchKernelGGL(k_integrate, dim3(grid), dim3(TSDF_THREADS), 0, ctx->stream, (const float *)v->zbuf.p, c, v->G, v->list.get(), v->counters.get(), v->vox.get());
+    if (rgb_u8)
+        hipLaunchKernelGGL(k_fuse_rgb, dim3(grid), dim3(TSDF_THREADS), 0, ctx->stream, (const float *)v->zbuf.p, (const uint8_t *)v->rgb_in.p, c, v->G,
+                           v->list.get(), v->counters.get(), v->vox.get(), v->col.get());
+    else
+        hipLaunchKernelGGL(k_integrate, dim3(grid), dim3(TSDF_THREADS), 0, ctx->stream, (const float *)v->zbuf.p, c, v->G, v->list.get(), v->counters.get(), v->vox.get());
     D2R_HIP(ctx, hipGetLastError());
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the caller's frame (pageable host memory) has been consumed
     v->have = false;
+    return D2R_OK;
+}
+
+int d2r_tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *mask_u8, uint32_t w, uint32_t h, const float *intrinsics,
+                       const float *cam_pose, uint32_t erode_k)
+{
+    if (!v || !depth_u16 || !mask_u8 || !intrinsics || !cam_pose) return tsdf_fail(v, D2R_ERR_INVALID, "null argument");
+    return tsdf_integrate(v, depth_u16, mask_u8, nullptr, w, h, intrinsics, cam_pose, erode_k);
+}
+
+int d2r_tsdf_integrate_rgb(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t *mask_u8, const uint8_t *rgb_u8, uint32_t w, uint32_t h,
+                           const float *intrinsics, const float *cam_pose, uint32_t erode_k)
+{
+    if (!v || !depth_u16 || !mask_u8 || !rgb_u8 || !intrinsics || !cam_pose) return tsdf_fail(v, D2R_ERR_INVALID, "null argument");
+    return tsdf_integrate(v, depth_u16, mask_u8, rgb_u8, w, h, intrinsics, cam_pose, erode_k);
+}
+
+int d2r_tsdf_read_colours(d2r_tsdf *v, uint32_t *n_blocks, float *colours)
+{
+    if (!v || !n_blocks) return tsdf_fail(v, D2R_ERR_INVALID, "null argument");
+    d2r_ctx *ctx = v->ctx;
+    if (!v->col.get())
+        return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_read_colours: the volume holds no colour (no frame came through d2r_tsdf_integrate_rgb)");
+    D2R_HIP(ctx, hipSetDevice(v->device));
+    std::vector<uint8_t> ever(v->n_blocks);
+    D2R_HIP(ctx, hipMemcpyAsync(ever.data(), v->ever.get(), v->n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint32_t> blocks;
+    for (uint32_t b = 0; b < v->n_blocks; ++b)
+        if (ever[b]) blocks.push_back(b);
+    const uint32_t cap = *n_blocks;
+    *n_blocks = (uint32_t)blocks.size();
+    if (!colours || blocks.empty()) return D2R_OK;
+    if (cap < blocks.size()) return d2r_fail(ctx, D2R_ERR_INVALID, "d2r_tsdf_read_colours: the buffer holds fewer blocks than are active");
+    D2rDev<uint32_t> d_blocks;
+    D2rDev<float> d_c;
+    D2rDrain drain{ctx->stream};
+    const size_t nb = blocks.size(), bytes = nb * D2R_TSDF_BLOCK_VOX * 12;
+    int rc;
+    if ((rc = d_blocks.alloc(ctx, nb * 4, TSDF_MEM)) || (rc = d_c.alloc(ctx, bytes, TSDF_MEM))) return rc;
+    D2R_HIP(ctx, hipMemcpyAsync(d_blocks.get(), blocks.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_tsdf_colours, dim3((uint32_t)nb), dim3(TSDF_THREADS), 0, ctx->stream, v->col.get(), v->G, d_blocks.get(), d_c.get());
+    D2R_HIP(ctx, hipGetLastError());
+    D2R_HIP(ctx, hipMemcpyAsync(colours, d_c.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+    D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return D2R_OK;
 }
 
@@ -760,3 +874,45 @@ int d2r_tsdf_solid_points(d2r_tsdf *v, float weight_threshold, uint32_t *n_point
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ the volume as tsdfvis.hip reads it
+
+bool d2r_tsdf_has_colour(const d2r_tsdf *v) { return v->col.get() != nullptr; }
+int d2r_tsdf_device(const d2r_tsdf *v) { return v->device; }
+
+int d2r_tsdf_dev(d2r_ctx *ctx, d2r_tsdf *v, D2rTsdfDev *out)
+{
+    const TsdfGrid &G = v->G;
+    if (v->box_frame != v->frame) {
+        std::vector<uint8_t> ever(v->n_blocks);
+        D2R_HIP(ctx, hipMemcpyAsync(ever.data(), v->ever.get(), v->n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+        D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+        for (uint32_t b = 0; b < v->n_blocks; ++b) {
+            if (!ever[b]) continue;
+            const int32_t q[3] = {(int32_t)(b % G.nb[0]), (int32_t)((b / G.nb[0]) % G.nb[1]), (int32_t)(b / (G.nb[0] * G.nb[1]))};
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::min(lo[a], q[a]);
+                hi[a] = std::max(hi[a], q[a]);
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            const bool none = lo[a] > hi[a];
+            v->box_lo[a] = none ? 0 : (G.b0[a] + lo[a]) * D2R_TSDF_BLOCK;
+            v->box_hi[a] = none ? -1 : (G.b0[a] + hi[a]) * D2R_TSDF_BLOCK + D2R_TSDF_BLOCK - 1;
+        }
+        v->box_frame = v->frame;
+    }
+    out->vox = v->vox.get();
+    out->col = v->col.get();
+    out->ever = v->ever.get();
+    for (int a = 0; a < 3; ++a) {
+        out->lo[a] = G.b0[a] * D2R_TSDF_BLOCK;
+        out->nv[a] = G.nv[a];
+        out->nb[a] = G.nb[a];
+        out->box_lo[a] = v->box_lo[a];
+        out->box_hi[a] = v->box_hi[a];
+    }
+    out->voxel = G.voxel;
+    return D2R_OK;
+}

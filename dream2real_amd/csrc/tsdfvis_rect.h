@@ -1,0 +1,59 @@
+// The host arithmetic of the colour-TSDF ray caster (tsdfvis.hip): a candidate's ray matrix and the frame
+// rectangle its movable volume can show in.  Pure fp64 arithmetic on the host; stands on its own with d2r_shared.h's 4x4 toolkit
+// (tests/tsdfvis_host_main.cpp).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+struct TvRect { int32_t x0, y0, x1, y1; };       // inclusive; x1 < x0: no pixel
+
+// rows 0..3 of a row-major 4x4: finite, R^T R = I to 1e-5, last row 0 0 0 1.  The tolerance is tight on purpose: the rule inverts
+// poses by transposition, and the rectangle below projects the box with the transposed inverses too; the two agree only as far as
+// the poses are orthogonal.  1e-5 of a volume some metres from its pose's origin is tens of micrometres, far inside the slack
+// (a voxel and a pixel); rotations built in fp32 are off by about 1e-7.
+inline bool tv_is_rigid(const float T[16])
+{
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(T[i])) return false;
+    double dev = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += (double)T[k * 4 + i] * (double)T[k * 4 + j];
+            dev = std::max(dev, fabs(d - (i == j ? 1.0 : 0.0)));
+        }
+    return dev <= 1e-5 && T[12] == 0.f && T[13] == 0.f && T[14] == 0.f && T[15] == 1.f;
+}
+
+// The pixels whose rays can meet the box [lo, hi] (metres, the volume's frame) when `to_cam` (rows 0..2 used) takes the volume's
+// frame to the camera's: the bounds of the eight projected corners, widened by a pixel and clipped to the frame.  `slack` (metres)
+// widens the box by what the kernel's fp32 sample points can be off.  A corner at or behind z = near, or anything not finite,
+// gives the whole frame; a box with lo > hi on an axis gives no pixel.
+inline TvRect tv_box_rect(const double to_cam[16], const double lo[3], const double hi[3], double slack, double fx, double fy, double cx,
+                          double cy, double near, int32_t W, int32_t H)
+{
+    const TvRect whole{0, 0, W - 1, H - 1}, none{0, 0, -1, -1};
+    for (int a = 0; a < 3; ++a)
+        if (!(lo[a] <= hi[a])) return (lo[a] > hi[a]) ? none : whole;      // NaN: whole
+    double umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
+    for (int k = 0; k < 8; ++k) {
+        const double p[3] = {(k & 1) ? hi[0] + slack : lo[0] - slack, (k & 2) ? hi[1] + slack : lo[1] - slack,
+                             (k & 4) ? hi[2] + slack : lo[2] - slack};
+        double q[3];
+        for (int r = 0; r < 3; ++r) q[r] = ((to_cam[r * 4] * p[0] + to_cam[r * 4 + 1] * p[1]) + to_cam[r * 4 + 2] * p[2]) + to_cam[r * 4 + 3];
+        if (!(q[2] > near) || !(q[2] > 0.0)) return whole;
+        const double u = fx * q[0] / q[2] + cx, v = fy * q[1] / q[2] + cy;
+        if (!std::isfinite(u) || !std::isfinite(v)) return whole;
+        umin = std::min(umin, u);
+        umax = std::max(umax, u);
+        vmin = std::min(vmin, v);
+        vmax = std::max(vmax, v);
+    }
+    // (the clamps keep the conversions to int defined)
+    const double x0 = std::max(floor(umin) - 1.0, 0.0), x1 = std::min(ceil(umax) + 1.0, (double)W - 1.0);
+    const double y0 = std::max(floor(vmin) - 1.0, 0.0), y1 = std::min(ceil(vmax) + 1.0, (double)H - 1.0);
+    if (x1 < x0 || y1 < y0) return none;
+    return TvRect{(int32_t)x0, (int32_t)y0, (int32_t)x1, (int32_t)y1};
+}

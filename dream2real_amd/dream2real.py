@@ -61,6 +61,18 @@ class PathConfig:
     width: int = 1280
     height: int = 720
     phys_backend: str = "hulls"                        # physics_utils.PHYS_BACKENDS; not a key of the reference's files
+    # VIS_BACKENDS; not a key of the reference's files.  An init-only variable stored as a plain attribute: dataclasses.fields() and
+    # asdict() keep listing the settings format's fields and phys_backend, as tests/test_engine_host.py pins them
+    vis_backend: dataclasses.InitVar[str] = "default"
+
+    VIS_BACKENDS = ("default", "tsdf")                 # default: NeRF snapshots, or the clouds of use_vis_pcds; tsdf: colour volumes, ray-cast
+
+    def __post_init__(self, vis_backend):
+        if vis_backend not in self.VIS_BACKENDS:
+            raise ValueError(f"vis_backend {vis_backend!r} is not one of {self.VIS_BACKENDS}")
+        if vis_backend == "tsdf" and self.use_vis_pcds:
+            raise ValueError('vis_backend "tsdf" and use_vis_pcds are two different visual models: set one of them')
+        self.vis_backend = vis_backend
 
     # engine keys read as they are; pcds_type, single_view_idx and phys_backend have their own rules below
     _ENGINE_KEYS = ("sample_res", "scene_type", "render_cam_pose_idx", "use_phys", "lazy_phys_mods", "use_cache_renders",
@@ -72,7 +84,7 @@ class PathConfig:
     def from_json(cls, config_file, data_dir, **overrides):
         """The reference's settings format (configs/*/*.json) as cfg.py:19-53, 75-81 reads it: the `engine` group and the
         frame size of the `camera` group; `trainer`, `vis`, `robot` and the rest are not read.  `single_view_idx` defaults
-        to 0, `pcds_type` is read only with `use_vis_pcds`, `engine.phys_backend` is this package's own optional key.  A key
+        to 0, `pcds_type` is read only with `use_vis_pcds`, `engine.phys_backend` and `engine.vis_backend` are this package's own optional keys.  A key
         the path needs and the file lacks is a KeyError naming group.key.  `overrides` set the fields no file carries
         (embodied, resolution, save_renders) or replace what was read."""
         with open(config_file) as f:
@@ -87,6 +99,7 @@ class PathConfig:
         fields["pcds_type"] = need("engine", "pcds_type") if fields["use_vis_pcds"] else None
         fields["single_view_idx"] = config["engine"].get("single_view_idx", 0)
         fields["phys_backend"] = config["engine"].get("phys_backend", "hulls")
+        fields["vis_backend"] = config["engine"].get("vis_backend", "default")
         fields["width"], fields["height"] = need("camera", "w"), need("camera", "h")
         fields.update(overrides)
         return cls(data_dir=data_dir, **fields)
@@ -238,8 +251,8 @@ class ImaginationEngine:
 
         if cfg.use_cache_cam_poses:                                                                               # :146-151
             opt_cam_poses = np.load(os.path.join(self.data_dir, "opt_cam_poses.npy"))
-        elif cfg.use_vis_pcds:
-            opt_cam_poses = np.asarray(loader.T_WC_data)           # the ablation renders clouds: no NeRF, no pose optimisation
+        elif cfg.use_vis_pcds or cfg.vis_backend == "tsdf":
+            opt_cam_poses = np.asarray(loader.T_WC_data)           # the ablation renders clouds, the TSDF backend volumes: no NeRF, no pose optimisation
             np.save(os.path.join(self.data_dir, "opt_cam_poses.npy"), opt_cam_poses)
         else:
             raise NotImplementedError("build_scene_model: optimised camera poses come out of NeRF training, which is not implemented; "
@@ -320,11 +333,12 @@ class ImaginationEngine:
         movable_obj.vis_model = TaskModel.create_movable_vis_model(
             self.scene_model, movable_obj, self.out_scene_bound_masks, os.path.join(self.data_dir, "movable_vis_mod/"),
             use_vis_pcds=cfg.use_vis_pcds, pcds_type=cfg.pcds_type, single_view_idx=cfg.single_view_idx, use_cache=cfg.use_cache_vis,
-            data_dir=self.data_dir, ctx=self.ctx)
+            data_dir=self.data_dir, ctx=self.ctx, vis_backend=cfg.vis_backend)
         task_bground_obj, task_bground_masks = TaskModel.create_task_bground_obj(
             self.scene_model, movable_obj, relevant_objs, self.out_scene_bound_masks, os.path.join(self.data_dir, "task_bground_vis_mod/"),
             use_vis_pcds=cfg.use_vis_pcds, pcds_type=cfg.pcds_type, single_view_idx=cfg.single_view_idx,
-            render_distractors=cfg.render_distractors, use_cache=cfg.use_cache_vis, data_dir=self.data_dir, ctx=self.ctx)
+            render_distractors=cfg.render_distractors, use_cache=cfg.use_cache_vis, data_dir=self.data_dir, ctx=self.ctx,
+            vis_backend=cfg.vis_backend)
 
         if cfg.lazy_phys_mods:                                                                                    # :274-277
             movable_obj.phys_model = movable_phys
@@ -391,7 +405,10 @@ class ImaginationEngine:
         else:                                                                                    # :324-326
             phys_check = lambda pose_batch, task_model, valid_so_far: torch.ones(len(pose_batch), dtype=torch.bool)
 
-        if cfg.use_vis_pcds and not cfg.use_cache_goal_pose:                                     # :329-332
+        if cfg.vis_backend == "tsdf" and not cfg.use_cache_goal_pose:
+            from .tsdf_visual_model import TsdfRenderer
+            self.renderer = TsdfRenderer(self.ctx)        # 336 x 336 through INTRINSICS_CLIP_VIEW, as the point-cloud renderer
+        elif cfg.use_vis_pcds and not cfg.use_cache_goal_pose:                                   # :329-332
             from .pcd_visual_model import PointCloudRenderer
             self.renderer = PointCloudRenderer(self.ctx)
         else:

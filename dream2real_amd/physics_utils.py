@@ -366,6 +366,27 @@ class TsdfVolume:
         self.ctx.check(self.ctx.lib.d2r_tsdf_integrate(self.h, _lib.ptr(d), _lib.ptr(m), d.shape[1], d.shape[0],
                                                        _lib.ptr(K), _lib.ptr(T), int(erode_k)))
 
+    def integrate_rgb(self, depth_u16, mask, rgb, intrinsics, cam_pose, erode_k: int):
+        """d2r_tsdf_integrate_rgb: `integrate` plus the frame's colours uint8 [h,w,3].  A volume takes its
+        frames through one of the two calls only."""
+        d = np.ascontiguousarray(depth_u16, np.uint16)
+        m = np.ascontiguousarray(mask, np.uint8)
+        c = np.ascontiguousarray(rgb, np.uint8)
+        assert d.ndim == 2 and m.shape == d.shape and c.shape == d.shape + (3,)
+        K = np.ascontiguousarray(np.asarray(_np(intrinsics), np.float64).reshape(9), np.float32)
+        T = np.ascontiguousarray(np.asarray(_np(cam_pose), np.float64).reshape(16), np.float32)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_integrate_rgb(self.h, _lib.ptr(d), _lib.ptr(m), _lib.ptr(c), d.shape[1], d.shape[0],
+                                                           _lib.ptr(K), _lib.ptr(T), int(erode_k)))
+
+    def read_colours(self):
+        """-> float32 [n,16,16,16,3] indexed [z][y][x][channel]: the colours of read_voxels' blocks, in its order."""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.d2r_tsdf_read_colours(self.h, C.byref(n), None))
+        cols = np.zeros((n.value, 16, 16, 16, 3), np.float32)
+        if n.value:
+            self.ctx.check(self.ctx.lib.d2r_tsdf_read_colours(self.h, C.byref(n), _lib.ptr(cols)))
+        return cols
+
     def read_voxels(self):
         """-> (block coordinates int32 [n,3] (x, y, z), tsdf float32 [n,16,16,16] indexed [z][y][x], weight likewise), the
         blocks any frame touched in (z, y, x) order."""

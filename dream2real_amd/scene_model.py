@@ -62,11 +62,15 @@ class TaskModel:
 
     @staticmethod
     def create_task_bground_obj(scene_model, movable_obj, relevant_objs, out_scene_bound_masks, save_dir, use_vis_pcds=False, pcds_type=None,
-                                single_view_idx=0, render_distractors=False, use_cache=False, data_dir=None, *, ctx):
+                                single_view_idx=0, render_distractors=False, use_cache=False, data_dir=None, *, ctx, vis_backend="default"):
         """-> (task_bground_obj, task_bground_masks uint8 [N,H,W]): 0 = task background, 1 = movable / distractor / out of scene."""
         lut = task_bground_lut(scene_model, movable_obj, relevant_objs, render_distractors)
         task_bground_masks = _lib.masks_lut(ctx, _np(scene_model.masks).astype(np.uint8), lut, _np(out_scene_bound_masks).astype(np.uint8))
-        if use_vis_pcds:
+        if vis_backend == "tsdf":
+            from .tsdf_visual_model import ERODE_BACKGROUND, get_vis_tsdfs
+            vis_model = get_vis_tsdfs(scene_model.rgbs, scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, task_bground_masks,
+                                      scene_model.scene_bounds, ctx=ctx, erode_k=ERODE_BACKGROUND)
+        elif use_vis_pcds:
             from .pcd_visual_model import get_vis_pcds
             vis_model = get_vis_pcds(scene_model.rgbs, scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, task_bground_masks, 1,
                                      scene_model.scene_bounds, save_dir=save_dir, vis=False, use_cache=use_cache, pcds_type=pcds_type,
@@ -87,8 +91,12 @@ class TaskModel:
 
     @staticmethod
     def create_movable_vis_model(scene_model, movable_obj, out_scene_bound_masks, save_dir, use_vis_pcds=False, pcds_type=None, single_view_idx=0,
-                                 use_cache=False, data_dir=None, *, ctx):
+                                 use_cache=False, data_dir=None, *, ctx, vis_backend="default"):
         movable_masks = TaskModel.movable_masks_of(scene_model, movable_obj, ctx=ctx)
+        if vis_backend == "tsdf":
+            from .tsdf_visual_model import ERODE_OBJECT, get_vis_tsdfs
+            return get_vis_tsdfs(scene_model.rgbs, scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, movable_masks,
+                                 scene_model.scene_bounds, ctx=ctx, erode_k=ERODE_OBJECT)
         if use_vis_pcds:
             from .pcd_visual_model import get_vis_pcds
             return get_vis_pcds(scene_model.rgbs, scene_model.depths, scene_model.opt_cam_poses, scene_model.intrinsics, movable_masks, 1,

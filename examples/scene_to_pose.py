@@ -1,6 +1,8 @@
 """A scan folder and a settings file in, the best pose out: the three calls of ImaginationEngine.
-    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy]
+    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--vis-backend tsdf] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy]
 --vis also writes best_pose_vis.png (and, without use_vis_pcds, cost_volume.png) into the folder.
+--vis-backend tsdf renders the candidates from colour-TSDF volumes fused from the scan instead of the settings
+file's visual model (NeRF snapshots, or point clouds with use_vis_pcds, which it switches off).
 --dump-thumbnails DIR writes the objects' captioning thumbnails as DIR/obj_<object>_<k>.png, to caption them elsewhere.
 --proposals FILE.npy --tracked FILE.npy stand in for the two segmentation models: the mask generator's recorded proposals, bool [M,W,H]
 for the first frame turned upright, and the tracker's recorded raw label images, uint8 [N,H,W]; the engine builds the first label image
@@ -21,6 +23,13 @@ if "--dump-thumbnails" in argv:
     at = argv.index("--dump-thumbnails")
     dump_dir = argv[at + 1]
     del argv[at:at + 2]
+backend = {}
+if "--vis-backend" in argv:
+    at = argv.index("--vis-backend")
+    backend = dict(vis_backend=argv[at + 1])
+    if argv[at + 1] == "tsdf":
+        backend.update(use_vis_pcds=False, pcds_type=None)
+    del argv[at:at + 2]
 recorded = {}
 for flag in ("--proposals", "--tracked"):
     if flag in argv:
@@ -31,7 +40,7 @@ if len(recorded) == 1:
     sys.exit("--proposals and --tracked come together")
 vis = "--vis" in argv
 config_file, data_dir, user_instr, clip_dir = [a for a in argv if a != "--vis"][:4]
-cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=not recorded, phys_backend="tsdf")
+cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=not recorded, phys_backend="tsdf", **backend)
 models = {}
 if recorded:
     import numpy as np

@@ -791,6 +791,60 @@ D2R_API int d2r_sdfphys_check(d2r_ctx *ctx, d2r_sdfphys *h, const d2r_phys_param
 /* Device-event times of the handle's last check: ms_out host [3] = upload, kernel, download, in milliseconds. */
 D2R_API int d2r_sdfphys_get_timing(d2r_ctx *ctx, const d2r_sdfphys *h, double *ms_out);
 
+/* ------------------------------------------------- the colour-TSDF visual model (vis_backend "tsdf")
+ *
+ * This package's own third visual backend beside the NeRF snapshots and the point-cloud ablation; nothing here stands where a
+ * stage of the reference stands.  A volume fused from RGB-D frames carries three fp32 colour channels per voxel, and a ray
+ * caster renders the K candidates of a pose grid from a background volume and a movable volume, dense and hole-free.
+ */
+
+/* d2r_tsdf_integrate with colour: rgb_u8 host [h][w][3].  (tsdf, weight) take exactly what d2r_tsdf_integrate gives them: the
+ * same bytes.  At exactly the voxels whose tsdf the frame updates, each colour channel takes c = (w c + (float)rgb[v][u][ch]) /
+ * (w + 1), w the weight before the increment, (u, v) the pixel the voxel projected to; fp32, nothing contracted.  The colour
+ * storage (12 bytes a voxel) is allocated by the first call; a volume whose state with it would pass the cap of
+ * d2r_tsdf_create is refused with D2R_ERR_UNSUPPORTED ("TSDF volume over the cap").  A volume takes frames through one of the
+ * two calls only: the other one is refused with D2R_ERR_INVALID ("mixes").  Synchronous. */
+D2R_API int d2r_tsdf_integrate_rgb(d2r_tsdf *vol, const uint16_t *depth_u16, const uint8_t *mask_u8, const uint8_t *rgb_u8, uint32_t w,
+                                   uint32_t h, const float *intrinsics, const float *cam_pose, uint32_t erode_k);
+
+/* Parity hook: the blocks of d2r_tsdf_read_voxels in its order, colours host [n][16][16][16][3] fp32 indexed [z][y][x][channel].
+ * *n_blocks: capacity on entry, count on return; colours NULL = count only.  D2R_ERR_INVALID for a volume without colour. */
+D2R_API int d2r_tsdf_read_colours(d2r_tsdf *vol, uint32_t *n_blocks, float *colours);
+
+/*
+ * Parity hook: K ray-cast frames to the host.  Both volumes carry colour; they may lie on different grids.
+ *   view          d2r_pcd_view with d2r_pcd_render's limits (point_size is checked and otherwise unused)
+ *   cam_pose      host [16] fp32 row-major camera-to-world pose, OpenCV convention (rigid)
+ *   obj_pose_now  host [16] the movable object's pose O when its volume was fused; obj_poses host [K][16] candidate poses P_k
+ *   frames_out    host [K][h][w][3] uint8; depth_out host [K][h][w] fp32 or NULL: the camera depth of the winning hit, +inf
+ *                 where neither volume is hit
+ * The rule: pixel (i, j) casts d_c = ((j - cx) / fx, (i - cy) / fy, 1); a volume stays put and the ray
+ * moves by M = cam_pose (background) or M_k = (O inv(P_k)) cam_pose (movable), composed in fp64 and rounded once; samples at
+ * t_s = near + s voxel up to depth 3; a sample is observed when the eight corners of its cell have weight >= weight_threshold;
+ * the hit is the first observed pair (value > 0, then value <= 0), its depth the linear zero crossing, its colour the trilinear
+ * colour there; the movable hit wins where it is strictly nearer than the background's; a pixel without a hit is black.
+ * K = 0 is valid.  Refused before any device work, outputs untouched: null arguments, a volume without colour (or of another
+ * device), a non-rigid or non-finite pose, a view outside the limits, weight_threshold not > 0, a voxel so small that a ray
+ * would take more than 2^20 samples (D2R_ERR_UNSUPPORTED).  Synchronous.
+ */
+D2R_API int d2r_tsdfvis_render(d2r_ctx *ctx, d2r_tsdf *bg_vol, d2r_tsdf *movable_vol, const d2r_pcd_view *view, const float *cam_pose,
+                               const float *obj_pose_now, const float *obj_poses, uint32_t K, float weight_threshold,
+                               uint8_t *frames_out, float *depth_out);
+
+/* The fused pass: d2r_tsdfvis_render's frames scored as d2r_pcd_render_score_host scores its own, in the same chunks; the frames
+ * never leave the device unless frames_out is given.  Logits equal d2r_clip_score_frames(frames, rot90 = 1) of the frames
+ * d2r_tsdfvis_render gives.  Synchronous. */
+D2R_API int d2r_tsdfvis_render_score_host(d2r_ctx *ctx, d2r_tsdf *bg_vol, d2r_tsdf *movable_vol, const d2r_clip *clip,
+                                          const d2r_pcd_view *view, const float *cam_pose, const float *obj_pose_now,
+                                          const float *obj_poses, uint32_t K, float weight_threshold, const float *text_embeds,
+                                          uint32_t C, float logit_scale, float *logits_out, uint8_t *frames_out);
+
+/* Device-event times of the context's last d2r_tsdfvis_render / d2r_tsdfvis_render_score_host with K > 0: ms_out host [4] = upload
+ * (matrices and rectangles), the background's cast, the candidates' casts summed over the passes, the copies of frames and depths
+ * to the host summed over the passes (parity hook; 0 for the fused call, whose frames stay on the device unless frames_out is
+ * given, and whose scoring is not in these figures), in milliseconds. */
+D2R_API int d2r_tsdfvis_get_timing(d2r_ctx *ctx, double *ms_out);
+
 /* 8-bit images of 1 (grey), 3 (RGB) or 4 (RGBA) interleaved channels -> a PNG file (mask files, the RGBA task images); a grey PNG
  * of 8 or 16 bits -> uint8 / uint16 [h][w] in host byte order (mask files, the 16-bit millimetre depth files; w, h: the expected
  * size, 0 = any); d2r_png_info reads the header.  Host only. */
