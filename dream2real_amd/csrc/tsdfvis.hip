@@ -281,12 +281,10 @@ int tv_prepare(d2r_ctx *ctx, d2r_tsdf *bg, d2r_tsdf *mv, const d2r_pcd_view *vie
     call.cam = TvCam{view->fx, view->fy, view->cx, view->cy, view->near, thr, (int32_t)view->width, (int32_t)view->height, 0};
     const TvCam &c = call.cam;
 
-    // M_k = (O inv(P_k)) cam_pose in fp64, rounded once; its inverse inv(cam_pose) (P_k inv(O)) projects the movable volume's box
-    double C4[16], Ci[16], O4[16], Oi[16], P4[16], Pi[16], T[16], M[16], Minv[16];
+    // M_k = (O inv(P_k)) cam_pose in fp64, rounded once; the true fp64 inverse of the rounded matrix projects the movable volume's box
+    double C4[16], O4[16], Pi[16], T[16], M[16], Minv[16];
     d2r_load16(cam_pose, C4);
     d2r_load16(obj_pose_now, O4);
-    d2r_rigid_inverse4(cam_pose, Ci);
-    d2r_rigid_inverse4(obj_pose_now, Oi);
     std::vector<TvMat> mats(1 + (size_t)K);
     std::vector<TvRect> rects(std::max<uint32_t>(K, 1), TvRect{0, 0, -1, -1});
     d2r_round34(C4, mats[0].m);
@@ -299,13 +297,11 @@ int tv_prepare(d2r_ctx *ctx, d2r_tsdf *bg, d2r_tsdf *mv, const d2r_pcd_view *vie
         hi[a] = ((double)Dm.box_hi[a] + 2.0) * step;
     }
     for (uint32_t k = 0; k < K; ++k) {
-        d2r_load16(obj_poses + (size_t)k * 16, P4);
         d2r_rigid_inverse4(obj_poses + (size_t)k * 16, Pi);
         d2r_mul4(O4, Pi, T);
         d2r_mul4(T, C4, M);
         d2r_round34(M, mats[1 + k].m);
-        d2r_mul4(Ci, P4, T);
-        d2r_mul4(T, Oi, Minv);
+        tv_inverse34(mats[1 + k].m, Minv);
         // what an fp32 sample point o + t d can be off: a few ulps of |o| + t |d|
         const double omax = std::max(fabs(M[3]), std::max(fabs(M[7]), fabs(M[11])));
         const double slack = 4e-6 * (omax + t_end * (xmax + ymax + 1.0));

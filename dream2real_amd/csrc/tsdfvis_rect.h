@@ -1,4 +1,4 @@
-// The host arithmetic of the colour-TSDF ray caster (tsdfvis.hip): a candidate's ray matrix and the frame
+// The host arithmetic of the colour-TSDF ray caster (tsdfvis.hip): a candidate's ray matrix, its inverse and the frame
 // rectangle its movable volume can show in.  Pure fp64 arithmetic on the host; stands on its own with d2r_shared.h's 4x4 toolkit
 // (tests/tsdfvis_host_main.cpp).
 #pragma once
@@ -9,10 +9,10 @@
 
 struct TvRect { int32_t x0, y0, x1, y1; };       // inclusive; x1 < x0: no pixel
 
-// rows 0..3 of a row-major 4x4: finite, R^T R = I to 1e-5, last row 0 0 0 1.  The tolerance is tight on purpose: the rule inverts
-// poses by transposition, and the rectangle below projects the box with the transposed inverses too; the two agree only as far as
-// the poses are orthogonal.  1e-5 of a volume some metres from its pose's origin is tens of micrometres, far inside the slack
-// (a voxel and a pixel); rotations built in fp32 are off by about 1e-7.
+// rows 0..3 of a row-major 4x4: finite, R^T R = I to 1e-5, last row 0 0 0 1.  The rule inverts poses by transposition, so a pose
+// that is off orthogonal by e moves what the kernel marches by about e times the distance to that pose's origin; that is the
+// caller's to bound (rotations built in fp32 are off by about 1e-7).  The rectangle below does not lean on the tolerance: it is
+// projected with the inverse of the very matrix the kernel marches with (tv_inverse34), however far the poses' origins lie.
 inline bool tv_is_rigid(const float T[16])
 {
     for (int i = 0; i < 16; ++i)
@@ -25,6 +25,23 @@ inline bool tv_is_rigid(const float T[16])
             dev = std::max(dev, fabs(d - (i == j ? 1.0 : 0.0)));
         }
     return dev <= 1e-5 && T[12] == 0.f && T[13] == 0.f && T[14] == 0.f && T[15] == 1.f;
+}
+
+// The fp64 inverse (row-major 4x4, last row 0 0 0 1) of the affine map whose rows 0..2 are the fp32 matrix m [3][4], by cofactors.
+// This is the true inverse of the rounded matrix the kernel marches with, not a product of transposed inverses: the two differ by
+// twice a pose's deviation from orthogonal times the distance to its origin, 18 mm for a pose scaled by 1 + 4.5e-6 two kilometres
+// from the origin, which cut pixels off the rectangle.  A singular or non-finite m gives NaNs: tv_box_rect then takes the whole frame.
+inline void tv_inverse34(const float m[12], double out[16])
+{
+    const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], i = m[10];
+    const double co[3][3] = {{e * i - f * h, c * h - b * i, b * f - c * e}, {f * g - d * i, a * i - c * g, c * d - a * f}, {d * h - e * g, b * g - a * h, a * e - b * d}};
+    const double det = (a * co[0][0] + b * co[1][0]) + c * co[2][0];
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) out[r * 4 + k] = co[r][k] / det;
+        out[r * 4 + 3] = -((out[r * 4] * (double)m[3] + out[r * 4 + 1] * (double)m[7]) + out[r * 4 + 2] * (double)m[11]);
+    }
+    out[12] = out[13] = out[14] = 0.0;
+    out[15] = 1.0;
 }
 
 // The pixels whose rays can meet the box [lo, hi] (metres, the volume's frame) when `to_cam` (rows 0..2 used) takes the volume's

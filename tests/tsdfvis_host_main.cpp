@@ -15,6 +15,15 @@ static int failures = 0;
 
 static bool same(TvRect r, int x0, int y0, int x1, int y1) { return r.x0 == x0 && r.y0 == y0 && r.x1 == x1 && r.y1 == y1; }
 
+// a candidate's rectangle as tv_prepare builds it: the box under the true inverse of the fp32 ray matrix m
+static TvRect rect_of(const float m[12], const double lo[3], const double hi[3], double slack, double fx, double fy, double cx, double cy,
+                      double near, int W, int H)
+{
+    double inv[16];
+    tv_inverse34(m, inv);
+    return tv_box_rect(inv, lo, hi, slack, fx, fy, cx, cy, near, W, H);
+}
+
 int main()
 {
     float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -71,6 +80,44 @@ int main()
     // a rotated transform: the camera looks back along -z from z = 3
     const double B[16] = {-1, 0, 0, 0, 0, 1, 0, 0, 0, 0, -1, 3, 0, 0, 0, 1};
     CHECK(same(tv_box_rect(B, lo, hi, 0.0, fx, fy, cx, cy, near, W, H), 39, 29, 51, 41));
+    // the inverse of a rigid matrix is its transposed inverse; of a singular or non-finite one, NaNs, and the whole frame
+    {
+        const float b[12] = {-1, 0, 0, 0, 0, 1, 0, 0, 0, 0, -1, 3};
+        double inv[16];
+        tv_inverse34(b, inv);
+        for (int i = 0; i < 16; ++i) CHECK(inv[i] == B[i]);
+        const float z[12] = {1, 0, 0, 0, 0, 1, 0, 0, 1, 1, 0, 0};
+        CHECK(same(rect_of(z, lo, hi, 0.0, fx, fy, cx, cy, near, W, H), 0, 0, W - 1, H - 1));
+        const float n[12] = {1, 0, 0, NAN, 0, 1, 0, 0, 0, 0, 1, 0};
+        CHECK(same(rect_of(n, lo, hi, 0.0, fx, fy, cx, cy, near, W, H), 0, 0, W - 1, H - 1));
+    }
+    // the rectangle inputs of tests/tsdfvis_edge_cases.py (the values tests/tsdfvis_ref.py's candidate_rect is given and gives)
+    {   // E8: a rectangle of one pixel
+        const float m[12] = {1.0, 0.0, 0.0, 0.19140625, 0.0, 1.0, 0.0, 0.2578125, 0.0, 0.0, 1.0, 0.0};
+        const double lo[3] = {-0.06640625, -0.06640625, 0.18359375}, hi[3] = {0.06640625, 0.06640625, 0.31640625};
+        CHECK(same(rect_of(m, lo, hi, 2.3031249999999997e-05, 24.0, 16.0, 8.0, 8.0, 0.0078125, 17, 17), 0, 0, 0, 0));
+    }
+    {   // E8: a rectangle that ends on column 15, a tile's last
+        const float m[12] = {1.0, 0.0, 0.0, 0.0234375, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+        const double lo[3] = {-0.06640625, -0.06640625, 0.18359375}, hi[3] = {0.06640625, 0.06640625, 0.31640625};
+        CHECK(same(rect_of(m, lo, hi, 2.209375e-05, 24.0, 16.0, 8.0, 8.0, 0.0078125, 17, 17), 0, 1, 15, 15));
+    }
+    {   // E8: a rectangle that starts on column 16, the next tile's first
+        const float m[12] = {1.0, 0.0, 0.0, -0.19140625, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+        const double lo[3] = {-0.06640625, -0.06640625, 0.18359375}, hi[3] = {0.06640625, 0.06640625, 0.31640625};
+        CHECK(same(rect_of(m, lo, hi, 2.2765625e-05, 24.0, 16.0, 8.0, 8.0, 0.0078125, 17, 17), 16, 1, 16, 15));
+    }
+    {   // E12: a pose scaled by 1 + 4.5e-6 two kilometres from the origin; the transposed inverses gave 30 .. 47 here
+        const float m[12] = {0.9999954700469971, 0.0, 0.0, 2047.92822265625, 0.0, 0.9999954700469971, 0.0, -1023.995361328125, 0.0, 0.0, 0.9999954700469971, 511.7476806640625};
+        const double lo[3] = {2047.93359375, -1024.06640625, 512.18359375}, hi[3] = {2048.06640625, -1023.93359375, 512.31640625};
+        CHECK(same(rect_of(m, lo, hi, 0.008204744141757488, 512.0, 512.0, 24.0, 20.0, 0.0078125, 48, 40), 19, 0, 47, 39));
+    }
+    {   // E12: the same scaled the other way
+        const float m[12] = {1.000004529953003, 0.0, 0.0, 2047.94677734375, 0.0, 1.000004529953003, 0.0, -1024.004638671875, 0.0, 0.0, 1.000004529953003, 511.7523193359375};
+        const double lo[3] = {2047.93359375, -1024.06640625, 512.18359375}, hi[3] = {2048.06640625, -1023.93359375, 512.31640625};
+        CHECK(same(rect_of(m, lo, hi, 0.008204818358242511, 512.0, 512.0, 24.0, 20.0, 0.0078125, 48, 40), 0, 0, 47, 39));
+    }
+
     if (failures == 0) printf("ok\n");
     return failures != 0;
 }
