@@ -93,6 +93,9 @@ PROTOTYPES = {
     "d2r_tsdfvis_render": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _f32, _ptr, _ptr)),
     "d2r_tsdfvis_render_score_host": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _f32, _ptr, _u32, _f32, _ptr, _ptr)),
     "d2r_tsdfvis_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_camtrack_system": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _f32, _u32, _ptr)),
+    "d2r_camtrack_refine": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_camtrack_get_timing": (_int, (_ptr, _ptr)),
     "d2r_png_write_channels": (_int, (_ptr, _u32, _u32, _u32, _str, _int)),
     "d2r_png_info": (_int, (_str, _ptr, _ptr, _ptr, _ptr)),
     "d2r_png_read_rgb": (_int, (_str, _u32, _u32, _ptr)),

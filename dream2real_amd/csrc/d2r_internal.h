@@ -142,6 +142,10 @@ struct d2r_ctx {
     D2rStageTimer tv_dl_timer;   // ... one pass's copy of frames and depths to the host (parity hook); tv_dl_ms sums the passes
     double tv_cast_ms = 0.0, tv_dl_ms = 0.0;
     bool tv_pass_pending = false, tv_dl_pending = false;
+    Buf ct_in, ct_ws;            // camtrack.hip: the uploaded depth + mask (one D2rStage), per-workgroup partial sums + the 29 sums
+    D2rStageTimer ct_timer, ct_it_timer;   // ... upload of the last refine, and one iteration's kernels / download; ct_ms sums the iterations (d2r_camtrack_get_timing)
+    double ct_ms[3] = {0.0, 0.0, 0.0};
+    bool ct_timed = false;
     Buf mv_in, mv_recs, mv_queue, mv_shade, mv_keys, mv_out;   // meshvis.hip: uploaded inputs (seven segments of a D2rStage), triangle records, the large-triangle queue, shade bytes, mesh + cube key buffers, rgb + ids of the current call
     Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots (the segments of a D2rStage per entry point), result frames, union-find parents + component statistics of a pass
     Buf thumb_in, thumb_ws, thumb_out;   // masks.hip, object thumbnails: frames + noise + records (one D2rStage), statistics / labelling / blur workspace, the packed thumbnails

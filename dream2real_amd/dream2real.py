@@ -64,15 +64,27 @@ class PathConfig:
     # VIS_BACKENDS; not a key of the reference's files.  An init-only variable stored as a plain attribute: dataclasses.fields() and
     # asdict() keep listing the settings format's fields and phys_backend, as tests/test_engine_host.py pins them
     vis_backend: dataclasses.InitVar[str] = "default"
+    # CAM_POSE_REFINES; not a key of the reference's files, held as vis_backend is
+    cam_pose_refine: dataclasses.InitVar[str] = "none"
 
     VIS_BACKENDS = ("default", "tsdf")                 # default: NeRF snapshots, or the clouds of use_vis_pcds; tsdf: colour volumes, ray-cast
+    CAM_POSE_REFINES = ("none", "tsdf")                # none: the loader's poses as they are; tsdf: refined against the volume fused so far
 
-    def __post_init__(self, vis_backend):
+    def __post_init__(self, vis_backend, cam_pose_refine):
         if vis_backend not in self.VIS_BACKENDS:
             raise ValueError(f"vis_backend {vis_backend!r} is not one of {self.VIS_BACKENDS}")
         if vis_backend == "tsdf" and self.use_vis_pcds:
             raise ValueError('vis_backend "tsdf" and use_vis_pcds are two different visual models: set one of them')
+        if cam_pose_refine not in self.CAM_POSE_REFINES:
+            raise ValueError(f"cam_pose_refine {cam_pose_refine!r} is not one of {self.CAM_POSE_REFINES}")
+        if cam_pose_refine == "tsdf" and self.use_cache_cam_poses:
+            raise ValueError('cam_pose_refine "tsdf" and use_cache_cam_poses conflict: the cached opt_cam_poses.npy would be read and '
+                             "nothing refined; set one of them")
+        if cam_pose_refine == "tsdf" and not (self.use_vis_pcds or vis_backend == "tsdf"):
+            raise ValueError('cam_pose_refine "tsdf" refines the loader\'s poses, which the engine takes only with use_vis_pcds or '
+                             'vis_backend "tsdf"; the NeRF backend expects the poses its training optimised')
         self.vis_backend = vis_backend
+        self.cam_pose_refine = cam_pose_refine
 
     # engine keys read as they are; pcds_type, single_view_idx and phys_backend have their own rules below
     _ENGINE_KEYS = ("sample_res", "scene_type", "render_cam_pose_idx", "use_phys", "lazy_phys_mods", "use_cache_renders",
@@ -84,7 +96,7 @@ class PathConfig:
     def from_json(cls, config_file, data_dir, **overrides):
         """The reference's settings format (configs/*/*.json) as cfg.py:19-53, 75-81 reads it: the `engine` group and the
         frame size of the `camera` group; `trainer`, `vis`, `robot` and the rest are not read.  `single_view_idx` defaults
-        to 0, `pcds_type` is read only with `use_vis_pcds`, `engine.phys_backend` and `engine.vis_backend` are this package's own optional keys.  A key
+        to 0, `pcds_type` is read only with `use_vis_pcds`, `engine.phys_backend`, `engine.vis_backend` and `engine.cam_pose_refine` are this package's own optional keys.  A key
         the path needs and the file lacks is a KeyError naming group.key.  `overrides` set the fields no file carries
         (embodied, resolution, save_renders) or replace what was read."""
         with open(config_file) as f:
@@ -100,6 +112,7 @@ class PathConfig:
         fields["single_view_idx"] = config["engine"].get("single_view_idx", 0)
         fields["phys_backend"] = config["engine"].get("phys_backend", "hulls")
         fields["vis_backend"] = config["engine"].get("vis_backend", "default")
+        fields["cam_pose_refine"] = config["engine"].get("cam_pose_refine", "none")
         fields["width"], fields["height"] = need("camera", "w"), need("camera", "h")
         fields.update(overrides)
         return cls(data_dir=data_dir, **fields)
@@ -253,6 +266,12 @@ class ImaginationEngine:
             opt_cam_poses = np.load(os.path.join(self.data_dir, "opt_cam_poses.npy"))
         elif cfg.use_vis_pcds or cfg.vis_backend == "tsdf":
             opt_cam_poses = np.asarray(loader.T_WC_data)           # the ablation renders clouds, the TSDF backend volumes: no NeRF, no pose optimisation
+            if cfg.cam_pose_refine == "tsdf":                      # ... but each frame tracked against the volume fused so far
+                from . import cam_pose_opt
+                opt_cam_poses, reports = cam_pose_opt.refine_cam_poses(depths, opt_cam_poses, intrinsics, self.out_scene_bound_masks,
+                                                                       cfg.scene_phys_bounds, ctx=self.ctx)
+                with open(os.path.join(self.data_dir, "cam_pose_refine.json"), "w") as f:
+                    json.dump(reports, f, indent=1)
             np.save(os.path.join(self.data_dir, "opt_cam_poses.npy"), opt_cam_poses)
         else:
             raise NotImplementedError("build_scene_model: optimised camera poses come out of NeRF training, which is not implemented; "

@@ -1,8 +1,10 @@
 """A scan folder and a settings file in, the best pose out: the three calls of ImaginationEngine.
-    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--vis-backend tsdf] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy]
+    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--vis-backend tsdf] [--refine-poses] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy]
 --vis also writes best_pose_vis.png (and, without use_vis_pcds, cost_volume.png) into the folder.
 --vis-backend tsdf renders the candidates from colour-TSDF volumes fused from the scan instead of the settings
 file's visual model (NeRF snapshots, or point clouds with use_vis_pcds, which it switches off).
+--refine-poses refines each frame's camera pose against the TSDF volume fused so far (it needs use_vis_pcds or
+--vis-backend tsdf, and no use_cache_cam_poses) and writes cam_pose_refine.json beside opt_cam_poses.npy.
 --dump-thumbnails DIR writes the objects' captioning thumbnails as DIR/obj_<object>_<k>.png, to caption them elsewhere.
 --proposals FILE.npy --tracked FILE.npy stand in for the two segmentation models: the mask generator's recorded proposals, bool [M,W,H]
 for the first frame turned upright, and the tracker's recorded raw label images, uint8 [N,H,W]; the engine builds the first label image
@@ -30,6 +32,9 @@ if "--vis-backend" in argv:
     if argv[at + 1] == "tsdf":
         backend.update(use_vis_pcds=False, pcds_type=None)
     del argv[at:at + 2]
+if "--refine-poses" in argv:
+    argv.remove("--refine-poses")
+    backend.update(cam_pose_refine="tsdf")
 recorded = {}
 for flag in ("--proposals", "--tracked"):
     if flag in argv:

@@ -845,6 +845,60 @@ D2R_API int d2r_tsdfvis_render_score_host(d2r_ctx *ctx, d2r_tsdf *bg_vol, d2r_ts
  * given, and whose scoring is not in these figures), in milliseconds. */
 D2R_API int d2r_tsdfvis_get_timing(d2r_ctx *ctx, double *ms_out);
 
+/* ------------------------------------------------- camera poses refined against a TSDF volume (cam_pose_refine "tsdf")
+ *
+ * This package's own stand-in for the camera poses NeRF training optimises in the reference: frame-to-model tracking on the signed
+ * distance field itself.  One linearisation: every pixel with u % stride == 0, v % stride == 0, a set mask and 0 < z = u16 / 1000
+ * <= 3 is back-projected through the fp32 pose; where the eight corners of its cell carry weight >= weight_threshold and the
+ * trilinear tsdf phi has |phi| < 1 (and the gates of section 2j hold) it contributes the residual r = phi trunc and the Jacobian
+ * row J = [n, p_w x n], n the analytic gradient of the trilinear interpolant in metres per metre, of the left-multiplied twist
+ * (T <- exp(xi^) T).  The 29 sums -- the upper triangle of J^T J row by row (21), J^T r (6), sum r^2, the count -- are signed 64-bit
+ * integers: each term is the exact fp64 product of two fp32 factors times 2^D2R_CAMTRACK_SCALE_LOG2 rounded to nearest even (the
+ * count is plain), so the sums are the same bits in any order.
+ */
+#define D2R_CAMTRACK_SUMS 29
+#define D2R_CAMTRACK_SCALE_LOG2 29
+#define D2R_CAMTRACK_MAX_ITERS 64
+enum { D2R_CAMTRACK_CONVERGED = 0, D2R_CAMTRACK_MAX_ITERS_REACHED = 1, D2R_CAMTRACK_DEGENERATE = 2, D2R_CAMTRACK_TOO_FEW = 3 };
+
+typedef struct d2r_camtrack_params {
+    float weight_threshold;   /* > 0; 1 while a scan is being fused frame by frame */
+    uint32_t stride;          /* >= 1 */
+    uint32_t max_iters;       /* 1 .. D2R_CAMTRACK_MAX_ITERS; 20 by default in the Python layer */
+    uint32_t min_pixels;      /* fewer contributing pixels than this in a linearisation: D2R_CAMTRACK_TOO_FEW */
+} d2r_camtrack_params;
+
+typedef struct d2r_camtrack_report {
+    int32_t status;           /* D2R_CAMTRACK_* */
+    uint32_t iters;           /* linearisations done: the valid entries of poses and sums */
+    uint64_t pixels_first, pixels_last;   /* contributing pixels of the first and the last linearisation */
+    double rms_first, rms_last;           /* sqrt(sum r^2 / count) of those two, metres */
+    float poses[64][16];      /* the fp32 pose each linearisation used */
+    int64_t sums[64][29];     /* ... and its sums */
+} d2r_camtrack_report;
+
+/* Parity hook: one linearisation.  depth_u16 host [h][w] millimetres, mask_u8 host [h][w] (non-zero = use; no erosion here),
+ * intrinsics host [9] row-major 3x3, cam_pose host [16] row-major camera-to-world, sums_out host [D2R_CAMTRACK_SUMS].  A volume
+ * fed through d2r_tsdf_integrate_rgb is accepted as well.  Refused with D2R_ERR_INVALID before any device work, sums_out
+ * untouched: null arguments, a volume of another device than ctx's, a non-rigid (R^T R = I to 1e-5, last row 0 0 0 1) or non-finite
+ * pose, non-finite intrinsics or a zero focal length, stride 0, w h = 0 or above 2^21, weight_threshold not > 0.  Synchronous. */
+D2R_API int d2r_camtrack_system(d2r_ctx *ctx, d2r_tsdf *vol, const uint16_t *depth_u16, const uint8_t *mask_u8, uint32_t w, uint32_t h,
+                                const float *intrinsics, const float *cam_pose, float weight_threshold, uint32_t stride,
+                                int64_t *sums_out);
+
+/* The loop: linearise at the pose rounded to fp32, solve the 6 x 6 system on the host in fp64 (LDL^T; a pivot <= 1e-6 of the
+ * largest diagonal entry is D2R_CAMTRACK_DEGENERATE and stops with the pose it had), T <- exp(xi^) T carried in fp64, until |v| <
+ * 1e-5 m and |omega| < 1e-5 rad, max_iters linearisations, or fewer than min_pixels contributing pixels (cam_pose_out = cam_pose_in
+ * bit for bit).  Depth and mask are uploaded once; each iteration brings 29 sums back.  cam_pose_out host [16].  Refusals as
+ * d2r_camtrack_system's plus max_iters 0 or above D2R_CAMTRACK_MAX_ITERS; cam_pose_out and report untouched.  Synchronous. */
+D2R_API int d2r_camtrack_refine(d2r_ctx *ctx, d2r_tsdf *vol, const uint16_t *depth_u16, const uint8_t *mask_u8, uint32_t w, uint32_t h,
+                                const float *intrinsics, const float *cam_pose_in, const d2r_camtrack_params *params,
+                                float *cam_pose_out, d2r_camtrack_report *report);
+
+/* Device-event times of the context's last d2r_camtrack_refine: ms_out host [3] = upload of depth and mask, the kernels summed
+ * over the iterations, the downloads of the sums summed over the iterations, in milliseconds. */
+D2R_API int d2r_camtrack_get_timing(d2r_ctx *ctx, double *ms_out);
+
 /* 8-bit images of 1 (grey), 3 (RGB) or 4 (RGBA) interleaved channels -> a PNG file (mask files, the RGBA task images); a grey PNG
  * of 8 or 16 bits -> uint8 / uint16 [h][w] in host byte order (mask files, the 16-bit millimetre depth files; w, h: the expected
  * size, 0 = any); d2r_png_info reads the header.  Host only. */
