@@ -1,12 +1,13 @@
 // camtrack.hip — camera poses refined against a TSDF volume (cam_pose_refine "tsdf"): frame-to-model tracking on the signed distance
 // field itself.  This package's own stand-in for the poses NeRF training optimises in the reference; nothing here stands where
 // reference code stands.  The rule is DESIGN.md section 2j, restated in numpy by tests/camtrack_ref.py and held to it by integer
-// equality: every fp32 step is one IEEE operation in the written order (the library is built with -ffp-contract=off), every term of
-// the 29 sums is the exact fp64 product of two fp32 factors, scaled by 2^29, rounded to nearest even and added as a 64-bit integer,
-// so the sums are the same bits whatever the order of the reduction.
-//   k_ct_linearise  one lane per selected pixel (grid-stride, at most two workgroups a CU): back-projection, four 16-byte loads for
-//                   the cell's eight (tsdf, weight) corners, the trilinear value and its analytic gradient, the gates, 29 integer
-//                   accumulators in registers; at the end a wave reduction, four waves through LDS, one row of partials a workgroup
+// equality; how a point meets the volume (its cell, the eight corners and the weight rule, the trilinear value and its gradient) is
+// tsdf_sample.h's, which tsdfvis.hip reads through too.  Every fp32 step is one IEEE operation in the written order (the library is
+// built with -ffp-contract=off), every term of the 29 sums is the exact fp64 product of two fp32 factors, scaled by 2^29, rounded to
+// nearest even and added as a 64-bit integer, so the sums are the same bits whatever the order of the reduction.
+//   k_ct_linearise  one lane per selected pixel (grid-stride, at most two workgroups a CU): back-projection, the cell's eight (tsdf,
+//                   weight) corners (x-adjacent ones come fused: four 16-byte loads), the trilinear value and its analytic gradient,
+//                   the gates, 29 integer accumulators in registers; at the end a wave reduction, four waves through LDS, one row of partials a workgroup
 //   k_ct_reduce     one workgroup adds the rows up
 // The 6 x 6 solve, the exponential and the loop run on the host in fp64 (camtrack_solve.h).  Ordinary vector stores, no atomics,
 // no scratch.
@@ -17,7 +18,6 @@
 
 #include "camtrack_solve.h"
 #include "d2r_internal.h"
-#include "tsdfvis_rect.h"
 
 static_assert(CT_SUMS == D2R_CAMTRACK_SUMS && CT_SCALE_LOG2 == D2R_CAMTRACK_SCALE_LOG2, "camtrack_solve.h and d2r.h disagree");
 
@@ -30,14 +30,6 @@ constexpr float CT_DEPTH_MAX = 3.0f;           // section 2c's depth validity
 // the gates that bound a term (section 2j): |n_a| <= 4, |p_w|_inf <= 8, |r| <= 1 -> |J_i| <= 64, every product <= 2^12
 constexpr float CT_N_MAX = 4.0f, CT_P_MAX = 8.0f, CT_R_MAX = 1.0f;
 
-struct CtVol {
-    const float2 *vox;                         // [nz][ny][nx] (tsdf, weight)
-    int32_t lo[3];                             // global coordinate of voxel 0
-    uint32_t nv[3];
-    float clo[3], chi[3];                      // a cell's lowest corner c lies in the grid with its neighbour for clo <= c <= chi
-    float voxel, trunc;
-};
-
 struct CtCam {
     float fx, fy, cx, cy, thr;
     int32_t W, H;
@@ -45,15 +37,13 @@ struct CtCam {
     float m[12];                               // cam_pose, rows 0..2
 };
 
-struct alignas(8) CtPair { float t0, w0, t1, w1; };     // two x-adjacent voxels: one 16-byte load
-
 __device__ __forceinline__ long long ct_term(float a, float b)
 {
     return __double2ll_rn(((double)a * (double)b) * CT_SCALE);       // the product is exact, the scaling is exact, one rounding
 }
 
 // selected pixel `idx` -> does it contribute; J = [n, p_w x n], r
-__device__ __forceinline__ bool ct_pixel(const CtVol &V, const CtCam &c, const uint16_t *__restrict__ depth, const uint8_t *__restrict__ mask,
+__device__ __forceinline__ bool ct_pixel(const D2rTsdfDev &V, const CtCam &c, const uint16_t *__restrict__ depth, const uint8_t *__restrict__ mask,
                                          uint32_t idx, float (&J)[6], float &r)
 {
     const uint32_t u = (idx % c.ws) * c.stride, v = (idx / c.ws) * c.stride;
@@ -61,36 +51,17 @@ __device__ __forceinline__ bool ct_pixel(const CtVol &V, const CtCam &c, const u
     const float z = (float)depth[px] / 1000.0f;
     bool ok = mask[px] != 0 && z > 0.f && z <= CT_DEPTH_MAX;
     const float xc = (((float)u - c.cx) / c.fx) * z, yc = (((float)v - c.cy) / c.fy) * z;
-    float p[3], f[3];
-    int q[3];
+    float p[3], f[3], t[8], g[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         p[a] = ((c.m[4 * a] * xc + c.m[4 * a + 1] * yc) + c.m[4 * a + 2] * z) + c.m[4 * a + 3];
-        const float g = p[a] / V.voxel, fl = floorf(g);
-        ok = ok && fl >= V.clo[a] && fl <= V.chi[a] && fabsf(p[a]) <= CT_P_MAX;      // NaN and the infinities fail
-        f[a] = g - fl;
-        q[a] = ok ? (int)fl - V.lo[a] : 0;
+        ok = ok && fabsf(p[a]) <= CT_P_MAX;                              // (NaN fails)
     }
-    if (!ok) return false;
-    const size_t base = ((size_t)q[2] * V.nv[1] + (size_t)q[1]) * V.nv[0] + (size_t)q[0];
-    const size_t sy = V.nv[0], sz = (size_t)V.nv[0] * V.nv[1];
-    const CtPair c00 = *(const CtPair *)(V.vox + base), c10 = *(const CtPair *)(V.vox + base + sy);
-    const CtPair c01 = *(const CtPair *)(V.vox + base + sz), c11 = *(const CtPair *)(V.vox + base + sz + sy);
-    const float thr = c.thr;
-    if (!(c00.w0 >= thr && c00.w1 >= thr && c10.w0 >= thr && c10.w1 >= thr && c01.w0 >= thr && c01.w1 >= thr && c11.w0 >= thr && c11.w1 >= thr))
-        return false;
-    // along x, then y, then z, each step a + f (b - a) (section 2i's order); the gradient is the derivative of that interpolant
-    const float e00 = c00.t1 - c00.t0, e10 = c10.t1 - c10.t0, e01 = c01.t1 - c01.t0, e11 = c11.t1 - c11.t0;
-    const float x00 = c00.t0 + f[0] * e00, x10 = c10.t0 + f[0] * e10, x01 = c01.t0 + f[0] * e01, x11 = c11.t0 + f[0] * e11;
-    const float d0 = x10 - x00, d1 = x11 - x01;
-    const float y0 = x00 + f[1] * d0, y1 = x01 + f[1] * d1;
-    const float gz = y1 - y0;
-    const float phi = y0 + f[2] * gz;
-    const float gy = d0 + f[2] * (d1 - d0);
-    const float ey0 = e00 + f[1] * (e10 - e00), ey1 = e01 + f[1] * (e11 - e01);
-    const float gx = ey0 + f[2] * (ey1 - ey0);
+    size_t base = 0;
+    if (!ok || !ts_cell<false>(V, p, base, f) || !ts_corners(V, base, c.thr, t)) return false;
+    const float phi = ts_lerp3_grad(t, f, g);
     r = phi * V.trunc;
-    const float n0 = (gx * V.trunc) / V.voxel, n1 = (gy * V.trunc) / V.voxel, n2 = (gz * V.trunc) / V.voxel;
+    const float n0 = (g[0] * V.trunc) / V.voxel, n1 = (g[1] * V.trunc) / V.voxel, n2 = (g[2] * V.trunc) / V.voxel;
     if (!(fabsf(phi) < 1.0f && fabsf(r) <= CT_R_MAX && fabsf(n0) <= CT_N_MAX && fabsf(n1) <= CT_N_MAX && fabsf(n2) <= CT_N_MAX)) return false;
     J[0] = n0;
     J[1] = n1;
@@ -102,7 +73,7 @@ __device__ __forceinline__ bool ct_pixel(const CtVol &V, const CtCam &c, const u
 }
 
 // partials [gridDim.x][CT_ROW]: the sums over the pixels this workgroup visited
-__global__ __launch_bounds__(CT_THREADS) void k_ct_linearise(CtVol V, CtCam c, const uint16_t *__restrict__ depth, const uint8_t *__restrict__ mask,
+__global__ __launch_bounds__(CT_THREADS) void k_ct_linearise(D2rTsdfDev V, CtCam c, const uint16_t *__restrict__ depth, const uint8_t *__restrict__ mask,
                                                              long long *__restrict__ partials)
 {
     long long acc[CT_SUMS];
@@ -166,10 +137,8 @@ int ct_check(d2r_ctx *ctx, const d2r_tsdf *vol, const uint16_t *depth, const uin
 {
     if (!ctx || !vol || !depth || !mask || !intrinsics || !pose) return d2r_fail(ctx, D2R_ERR_INVALID, "null argument");
     if (d2r_tsdf_device(vol) != ctx->device) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: the volume belongs to another device");
-    if (!tv_is_rigid(pose)) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: cam_pose must be a finite rigid transform");
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(intrinsics[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: intrinsics must be finite");
-    if (intrinsics[0] == 0.f || intrinsics[4] == 0.f) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: focal lengths must not be 0");
+    if (!d2r_is_rigid(pose)) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: cam_pose must be a finite rigid transform");
+    if (int rc = d2r_check_cam(ctx, "camera tracking", intrinsics, pose, 0)) return rc;       // (the pose is held to more, above)
     if (stride == 0) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: stride must be >= 1");
     if (w == 0 || h == 0 || (uint64_t)w * h > CT_MAX_PIXELS) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: a frame holds 1 .. 2^21 pixels");
     if (!(thr > 0.f) || !std::isfinite(thr)) return d2r_fail(ctx, D2R_ERR_INVALID, "camera tracking: weight_threshold must be > 0");
@@ -177,7 +146,7 @@ int ct_check(d2r_ctx *ctx, const d2r_tsdf *vol, const uint16_t *depth, const uin
 }
 
 struct CtCall {
-    CtVol V{};
+    D2rTsdfDev V{};                            // the cells of the whole grid: the block flags are not read
     CtCam c{};
     size_t o_depth = 0, o_mask = 0, o_part = 0, o_sums = 0;
     uint32_t grid = 0;
@@ -188,23 +157,9 @@ int ct_upload(d2r_ctx *ctx, d2r_tsdf *vol, const uint16_t *depth, const uint8_t 
               uint32_t stride, CtCall &call)
 {
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    D2rTsdfDev D;
     int rc;
-    if ((rc = d2r_tsdf_dev(ctx, vol, &D))) return rc;
-    int32_t b0[3];
-    uint32_t nv[3];
-    float voxel, trunc;
-    if ((rc = d2r_tsdf_grid(vol, b0, nv, &voxel, &trunc))) return rc;
-    CtVol &V = call.V;
-    V.vox = D.vox;
-    for (int a = 0; a < 3; ++a) {
-        V.lo[a] = D.lo[a];
-        V.nv[a] = D.nv[a];
-        V.clo[a] = (float)D.lo[a];                                   // |coordinates| <= 2^24 + 2^20: exact
-        V.chi[a] = (float)(D.lo[a] + (int32_t)D.nv[a] - 2);
-    }
-    V.voxel = voxel;
-    V.trunc = trunc;
+    if ((rc = d2r_tsdf_dev(ctx, vol, &call.V))) return rc;
+    call.V.cells_of_grid();
     CtCam &c = call.c;
     c.fx = K[0];
     c.fy = K[4];

@@ -12,6 +12,7 @@
 
 #include "../../include/d2r.h"
 #include "d2r_shared.h"
+#include "tsdf_sample.h"
 
 class D2rJobPool;   // pngio.h
 struct D2rPngBase;  // pngio.h
@@ -256,20 +257,11 @@ struct PerDeviceOnce {
     void run(int device, F &&fn) { std::call_once(flag[device % D2R_MAX_DEVICES], fn); }
 };
 
-// tsdf.hip: a volume as the ray caster (tsdfvis.hip) reads it.  box: the voxels (global coordinates, inclusive) of the blocks any
-// frame touched, lo > hi when there is none; every voxel outside it has weight 0.
-struct D2rTsdfDev {
-    const float2 *vox;           // [nz][ny][nx] (tsdf, weight)
-    const float *col;            // [nz][ny][nx][3], nullptr for a volume without colour
-    const uint8_t *ever;         // [nbz][nby][nbx] non-zero: some frame touched the block
-    int32_t lo[3];               // global coordinate of voxel 0 per axis
-    uint32_t nv[3], nb[3];
-    int32_t box_lo[3], box_hi[3];
-    float voxel;
-};
+// tsdf.hip: a volume as its readers (tsdfvis.hip, camtrack.hip) see it: D2rTsdfDev of tsdf_sample.h, which kernels take by value
 bool d2r_tsdf_has_colour(const d2r_tsdf *v);
 int d2r_tsdf_device(const d2r_tsdf *v);
-int d2r_tsdf_dev(d2r_ctx *ctx, d2r_tsdf *v, D2rTsdfDev *out);     // reads the block flags back when frames arrived since the last call (synchronises)
+float d2r_tsdf_voxel(const d2r_tsdf *v);
+int d2r_tsdf_dev(d2r_ctx *ctx, d2r_tsdf *v, D2rTsdfDev *out);     // reads the block flags back when frames arrived since the last call (synchronises); the cells are the box's (cells_of_box)
 
 int d2r_pcd_check_view(d2r_ctx *ctx, const d2r_pcd_view *view);      // pcd.hip: the limits d2r_pcd_render holds a view to (meshvis.hip shares them)
 

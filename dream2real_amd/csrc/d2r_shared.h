@@ -1,9 +1,12 @@
 // What the geometry units (pcd.hip, pcdbuild.hip, meshvis.hip, masks.hip, tsdf.hip, sdfphys.hip, phys.hip, rectify.hip, the ray sort of
 // nerf.hip, d2r_nerf) share.  On the device: the single-workgroup scan and reduction.  On the host: an owner for device memory, the
 // fp64 4x4 toolkit, the layout of a staging buffer and its binder, the stage timer, the camera refusals of a batch of frames.  A piece
-// moves here when a second unit needs it.  Stands on its own (tests/shared_host_main.cpp) and comes with d2r_internal.h.
+// moves here when a second unit needs it.  Stands on its own (tests/shared_host_main.cpp) and comes with d2r_internal.h.  A plain
+// host compiler (tests/tsdfvis_host_main.cpp) gets the parts that need nothing from HIP: the 4x4 toolkit, the layout, the refusals.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #include <algorithm>
@@ -17,6 +20,8 @@ struct D2rBuf { void *p = nullptr; size_t cap = 0; };
 
 int d2r_fail(d2r_ctx *ctx, int code, const std::string &msg);      // api.hip
 int d2r_reserve(d2r_ctx *ctx, D2rBuf &b, size_t bytes);            // api.hip
+
+#if defined(__HIPCC__)
 hipStream_t d2r_stream(const d2r_ctx *ctx);                        // api.hip: ctx->stream, for the code here that sees d2r_ctx incomplete
 
 #define D2R_HIP(ctx, expr)                                                              \
@@ -130,6 +135,7 @@ __device__ __forceinline__ T d2r_block_sum(T mine)
     }
     return part[0];
 }
+#endif      // __HIPCC__
 
 // ------------------------------------------------------------------------------------------------ c. the fp64 4x4 toolkit
 
@@ -159,6 +165,23 @@ inline void d2r_mul4(const double A[16], const double B[16], double C[16])
             C[i * 4 + j] = ((A[i * 4 + 0] * B[0 * 4 + j] + A[i * 4 + 1] * B[1 * 4 + j]) + A[i * 4 + 2] * B[2 * 4 + j]) + A[i * 4 + 3] * B[3 * 4 + j];
 }
 
+// rows 0..3 of a row-major 4x4: finite, R^T R = I to 1e-5, last row 0 0 0 1 (the ray caster's and the camera tracker's refusal).
+// Their rules invert poses by transposition, so a pose that is off orthogonal by e moves what a kernel reads by about e times the
+// distance to that pose's origin; that is the caller's to bound (rotations built in fp32 are off by about 1e-7).
+inline bool d2r_is_rigid(const float T[16])
+{
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(T[i])) return false;
+    double dev = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += (double)T[k * 4 + i] * (double)T[k * 4 + j];
+            dev = std::max(dev, fabs(d - (i == j ? 1.0 : 0.0)));
+        }
+    return dev <= 1e-5 && T[12] == 0.f && T[13] == 0.f && T[14] == 0.f && T[15] == 1.f;
+}
+
 // float[16] -> double[16]; rows 0..2 rounded once into the float[12] a kernel-side matrix struct (PcdMat, MvMat) holds
 inline void d2r_load16(const float p[16], double out[16]) { for (int i = 0; i < 16; ++i) out[i] = (double)p[i]; }
 inline void d2r_round34(const double T[16], float out[12]) { for (int i = 0; i < 12; ++i) out[i] = (float)T[i]; }
@@ -180,6 +203,7 @@ struct D2rLayout {
     size_t total() const { return end; }      // the end of the last segment: the bytes to reserve
 };
 
+#if defined(__HIPCC__)
 // A layout bound to the workspace it describes: add() the segments, reserve(), then at<T>() and upload() by offset.
 class D2rStage : public D2rLayout {
 public:
@@ -235,12 +259,14 @@ private:
     hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed_ = false;
 };
+#endif      // __HIPCC__
 
 // ------------------------------------------------------------------------------------------------ e. a frame batch's camera
 
-// masks.hip (float poses) and pcdbuild.hip (double) refuse alike, `unit` in front of the message: 3x3 intrinsics, n row-major 4x4 poses
-template <class P>
-int d2r_check_cam(d2r_ctx *ctx, const char *unit, const double *K, const P *poses, uint32_t n)
+// Every unit that takes a camera refuses alike, `unit` in front of the message: 3x3 intrinsics, n row-major 4x4 poses, each float
+// or double.  A unit that holds its pose to more (tsdf.hip, camtrack.hip) passes n = 0 and says so itself.
+template <class I, class P>
+int d2r_check_cam(d2r_ctx *ctx, const char *unit, const I *K, const P *poses, uint32_t n)
 {
     for (int i = 0; i < 9; ++i)
         if (!std::isfinite(K[i])) return d2r_fail(ctx, D2R_ERR_INVALID, std::string(unit) + ": intrinsics must be finite");

@@ -232,6 +232,7 @@ int d2r_sdfphys_check(d2r_ctx *ctx, d2r_sdfphys *h, const d2r_phys_params *prm, 
     if (int rc = d2r_phys_orientations(ctx, prm, N, &oris)) return rc;
     SdfCheckParams P;
     // init_pose must be rigid to 1e-3 for its inverse to be [R^T | -R^T t]
+    // (not d2r_is_rigid: that one holds to 1e-5 and a finite translation, and would refuse poses this call has always taken)
     const float *I = prm->init_pose;
     double dev = 0.0;
     for (int i = 0; i < 3; ++i)

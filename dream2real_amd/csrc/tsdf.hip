@@ -617,11 +617,9 @@ static int tsdf_integrate(d2r_tsdf *v, const uint16_t *depth_u16, const uint8_t 
     d2r_ctx *ctx = v->ctx;
     if (w == 0 || h == 0 || w > 16384 || h > 16384) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: width and height must be 1 .. 16384");
     if (erode_k < 1 || erode_k > D2R_TSDF_MAX_ERODE) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: erode_k must be 1 .. 32");
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(intrinsics[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: intrinsics must be finite");
+    if (int rc = d2r_check_cam(ctx, "TSDF frame", intrinsics, cam_pose, 0)) return rc;
     for (int i = 0; i < 16; ++i)
         if (!std::isfinite(cam_pose[i])) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: cam_pose must be finite");
-    if (intrinsics[0] == 0.f || intrinsics[4] == 0.f) return d2r_fail(ctx, D2R_ERR_INVALID, "TSDF frame: focal lengths must not be 0");
     if (v->frame == 0xfffffffeu) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "TSDF volume: too many frames");
     if (v->frames != d2r_tsdf::FRAMES_NONE && (v->frames == d2r_tsdf::FRAMES_RGB) != (rgb_u8 != nullptr))
         return d2r_fail(ctx, D2R_ERR_INVALID,
@@ -875,10 +873,11 @@ int d2r_tsdf_solid_points(d2r_tsdf *v, float weight_threshold, uint32_t *n_point
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------------ the volume as tsdfvis.hip reads it
+// ------------------------------------------------------------------------------------------------ the volume as its readers see it
 
 bool d2r_tsdf_has_colour(const d2r_tsdf *v) { return v->col.get() != nullptr; }
 int d2r_tsdf_device(const d2r_tsdf *v) { return v->device; }
+float d2r_tsdf_voxel(const d2r_tsdf *v) { return v->G.voxel; }
 
 int d2r_tsdf_dev(d2r_ctx *ctx, d2r_tsdf *v, D2rTsdfDev *out)
 {
@@ -903,7 +902,7 @@ int d2r_tsdf_dev(d2r_ctx *ctx, d2r_tsdf *v, D2rTsdfDev *out)
         }
         v->box_frame = v->frame;
     }
-    out->vox = v->vox.get();
+    out->vox = (const TsVoxel *)v->vox.get();
     out->col = v->col.get();
     out->ever = v->ever.get();
     for (int a = 0; a < 3; ++a) {
@@ -914,5 +913,7 @@ int d2r_tsdf_dev(d2r_ctx *ctx, d2r_tsdf *v, D2rTsdfDev *out)
         out->box_hi[a] = v->box_hi[a];
     }
     out->voxel = G.voxel;
+    out->trunc = G.trunc;
+    out->cells_of_box();
     return D2R_OK;
 }

@@ -9,24 +9,9 @@
 
 struct TvRect { int32_t x0, y0, x1, y1; };       // inclusive; x1 < x0: no pixel
 
-// rows 0..3 of a row-major 4x4: finite, R^T R = I to 1e-5, last row 0 0 0 1.  The rule inverts poses by transposition, so a pose
-// that is off orthogonal by e moves what the kernel marches by about e times the distance to that pose's origin; that is the
-// caller's to bound (rotations built in fp32 are off by about 1e-7).  The rectangle below does not lean on the tolerance: it is
-// projected with the inverse of the very matrix the kernel marches with (tv_inverse34), however far the poses' origins lie.
-inline bool tv_is_rigid(const float T[16])
-{
-    for (int i = 0; i < 16; ++i)
-        if (!std::isfinite(T[i])) return false;
-    double dev = 0.0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double d = 0.0;
-            for (int k = 0; k < 3; ++k) d += (double)T[k * 4 + i] * (double)T[k * 4 + j];
-            dev = std::max(dev, fabs(d - (i == j ? 1.0 : 0.0)));
-        }
-    return dev <= 1e-5 && T[12] == 0.f && T[13] == 0.f && T[14] == 0.f && T[15] == 1.f;
-}
-
+// The poses are rigid to 1e-5 (d2r_is_rigid); the rectangle below does not lean on that tolerance: it is projected with the inverse
+// of the very matrix the kernel marches with, however far the poses' origins lie.
+//
 // The fp64 inverse (row-major 4x4, last row 0 0 0 1) of the affine map whose rows 0..2 are the fp32 matrix m [3][4], by cofactors.
 // This is the true inverse of the rounded matrix the kernel marches with, not a product of transposed inverses: the two differ by
 // twice a pose's deviation from orthogonal times the distance to its origin, 18 mm for a pose scaled by 1 + 4.5e-6 two kilometres

@@ -1,8 +1,9 @@
 """numpy restatement of the camera-pose refinement -- the oracle of tests/test_camtrack_*.py.
 
-The product does not import this module and this module imports nothing from the product.  The linearisation is fp32, one IEEE
-operation at a time in the rule's order (numpy does not contract); each of the 29 sums adds rint(fp64(a) * fp64(b) * 2^29) as
-integers, so the GPU's sums can be compared by integer equality.  The step (LDL^T, exp, the pose update) is Python floats (fp64) in
+The product does not import this module and this module imports nothing from the product.  How a point meets the volume (cell,
+fractions, the trilinear value and its gradient) is tests/tsdf_ref.py's cell and lerp3_grad, which tests/tsdfvis_ref.py builds on
+too.  The linearisation is fp32, one IEEE operation at a time in the rule's order (numpy does not contract); each of the 29 sums
+adds rint(fp64(a) * fp64(b) * 2^29) as integers, so the GPU's sums can be compared by integer equality.  The step (LDL^T, exp, the pose update) is Python floats (fp64) in
 csrc/camtrack_solve.h's order, with math.sin / math.sqrt (the C library's, as the host code uses).
 
   pixel      (u, v) with u % stride == 0, v % stride == 0, mask set, 0 < z = u16 / 1000 <= 3
@@ -19,6 +20,8 @@ from __future__ import annotations
 import math
 
 import numpy as np
+
+from tests import tsdf_ref
 
 f32 = np.float32
 SUMS = 29
@@ -72,40 +75,26 @@ def rows(grid, depth_u16, mask, intrinsics, pose, thr=1.0, stride=1, facts=None,
     valid = ok.copy()
     xc = ((uu.astype(np.float32) - cx) / fx) * z
     yc = ((vv.astype(np.float32) - cy) / fy) * z
-    p, f, q = [], [], []
     with np.errstate(all="ignore"):
+        p = np.stack([((M[a, 0] * xc + M[a, 1] * yc) + M[a, 2] * z) + M[a, 3] for a in range(3)], 1).astype(np.float32)
+    last = grid.lo + grid.nv - 2                                     # c and c + 1 lie in the grid on every axis
+    inside, c, f = tsdf_ref.cell(p, grid.voxel, grid.lo, last)
+    if facts is not None:
         for a in range(3):
-            pa = ((M[a, 0] * xc + M[a, 1] * yc) + M[a, 2] * z) + M[a, 3]
-            g = pa / grid.voxel
-            c = np.floor(g)
-            inside = (c >= f32(grid.lo[a])) & (c <= f32(grid.lo[a] + grid.nv[a] - 2))
-            if facts is not None:
-                facts.setdefault("outside", np.zeros(3, np.int64))[a] += int((valid & ~inside).sum())
-                facts.setdefault("last_cell", np.zeros(3, np.int64))[a] += int((valid & (c == f32(grid.lo[a] + grid.nv[a] - 2))).sum())
-                facts.setdefault("frac0", np.zeros(3, np.int64))[a] += int((valid & inside & (g == c)).sum())
-                facts.setdefault("negative", np.zeros(3, np.int64))[a] += int((valid & inside & (g < 0)).sum())
-            ok &= inside & (np.abs(pa) <= P_MAX)
-            p.append(pa.astype(np.float32))
-            f.append((g - c).astype(np.float32))
-            q.append(np.where(ok, c, f32(grid.lo[a])).astype(np.int64) - int(grid.lo[a]))
+            facts.setdefault("outside", np.zeros(3, np.int64))[a] += int((valid & ~inside[:, a]).sum())
+            facts.setdefault("last_cell", np.zeros(3, np.int64))[a] += int((valid & (c[:, a] == f32(last[a]))).sum())
+            facts.setdefault("frac0", np.zeros(3, np.int64))[a] += int((valid & inside[:, a] & (f[:, a] == 0)).sum())
+            facts.setdefault("negative", np.zeros(3, np.int64))[a] += int((valid & inside[:, a] & (c[:, a] < 0)).sum())
+    ok &= inside.all(axis=1) & (np.abs(p) <= P_MAX).all(axis=1)
     in_grid = ok.copy()
-    for a in range(3):
-        q[a] = np.where(ok, q[a], 0)
+    q = [np.where(ok, c[:, a], f32(grid.lo[a])).astype(np.int64) - int(grid.lo[a]) for a in range(3)]
     t = [grid.tsdf[q[2] + (k >> 2), q[1] + ((k >> 1) & 1), q[0] + (k & 1)] for k in range(8)]
     for k in range(8):
         ok &= grid.w[q[2] + (k >> 2), q[1] + ((k >> 1) & 1), q[0] + (k & 1)] >= f32(thr)
     observed = ok.copy()
-    f0, f1, f2 = f
+    phi, (gx, gy, gz) = tsdf_ref.lerp3_grad(t, f)
+    p = [p[:, a] for a in range(3)]
     with np.errstate(all="ignore"):
-        e00, e10, e01, e11 = t[1] - t[0], t[3] - t[2], t[5] - t[4], t[7] - t[6]
-        x00, x10, x01, x11 = t[0] + f0 * e00, t[2] + f0 * e10, t[4] + f0 * e01, t[6] + f0 * e11
-        d0, d1 = x10 - x00, x11 - x01
-        y0, y1 = x00 + f1 * d0, x01 + f1 * d1
-        gz = y1 - y0
-        phi = y0 + f2 * gz
-        gy = d0 + f2 * (d1 - d0)
-        ey0, ey1 = e00 + f1 * (e10 - e00), e01 + f1 * (e11 - e01)
-        gx = ey0 + f2 * (ey1 - ey0)
         r = phi * grid.trunc
         n = [(ga * grid.trunc) / grid.voxel for ga in (gx, gy, gz)]
         ok &= np.abs(phi) < f32(1)
@@ -116,7 +105,7 @@ def rows(grid, depth_u16, mask, intrinsics, pose, thr=1.0, stride=1, facts=None,
                          ("phi_pm1", (observed & (np.abs(phi) == f32(1))).sum()), ("gated", (ok & ~keep).sum()), ("contributing", keep.sum())):
             facts[key] = facts.get(key, 0) + int(val)
     if full:           # every selected pixel: (contributes bool [n], J [n,6], r [n], fractions [n,3]); rows that do not contribute hold garbage
-        return keep, np.stack(J, 1).astype(np.float32), r.astype(np.float32), np.stack(f, 1)
+        return keep, np.stack(J, 1).astype(np.float32), r.astype(np.float32), f
     return np.stack([j[keep] for j in J], 1).astype(np.float32), r[keep].astype(np.float32)
 
 

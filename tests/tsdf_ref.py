@@ -323,6 +323,40 @@ def rigid_inverse34(T, dtype=np.float64):
     return out.astype(np.float32)
 
 
+# ---------------------------------------------------------------------------------------------------- a point meets a volume
+# csrc/tsdf_sample.h restated; tests/tsdfvis_ref.py and tests/camtrack_ref.py build on these two.
+
+def cell(p, voxel, clo, chi):
+    """ts_cell's arithmetic: p float32 [n,3], voxel float32, clo / chi int [3] (global voxel indices, x y z) -> (inside bool [n,3]: per
+    axis clo <= c <= chi, NaN and the infinities fail; c float32 [n,3] = floor(p / voxel); fractions float32 [n,3] = p / voxel - c)."""
+    with np.errstate(all="ignore"):
+        g = np.asarray(p, np.float32) / f32(voxel)
+        c = np.floor(g)
+        fr = (g - c).astype(np.float32)
+        inside = np.stack([(c[:, a] >= f32(clo[a])) & (c[:, a] <= f32(chi[a])) for a in range(3)], 1)
+    return inside, c, fr
+
+
+def lerp3_grad(t, fr):
+    """ts_lerp3_grad: t the eight corners (k = x + 2 y + 4 z; [n] each, or [n,ch]), fr float32 [n,3] -> (value, (gx, gy, gz)): along
+    x, then y, then z, each step a + f (b - a); the gradient is the derivative of that interpolant by each fraction."""
+    f0, f1, f2 = (fr[:, a] if t[0].ndim == 1 else fr[:, a:a + 1] for a in range(3))
+    with np.errstate(all="ignore"):
+        e00, e10, e01, e11 = t[1] - t[0], t[3] - t[2], t[5] - t[4], t[7] - t[6]
+        x00, x10, x01, x11 = t[0] + f0 * e00, t[2] + f0 * e10, t[4] + f0 * e01, t[6] + f0 * e11
+        d0, d1 = x10 - x00, x11 - x01
+        y0, y1 = x00 + f1 * d0, x01 + f1 * d1
+        gz = y1 - y0
+        gy = d0 + f2 * (d1 - d0)
+        ey0, ey1 = e00 + f1 * (e10 - e00), e01 + f1 * (e11 - e01)
+        gx = ey0 + f2 * (ey1 - ey0)
+        return y0 + f2 * gz, (gx, gy, gz)
+
+
+def lerp3(t, fr):
+    return lerp3_grad(t, fr)[0]
+
+
 class Volume:
     def __init__(self, bounds, voxel=0.002, trunc=None, rules=(), probe=False):
         """rules: names from WRONG_RULES (default: the rule as written).  probe: record in self.probe what the rule touches on

@@ -1,7 +1,8 @@
-// The ray caster's host arithmetic (dream2real_amd/csrc/tsdfvis_rect.h) in a program of its own: tests/test_tsdfvis_host.py
+// The ray caster's host arithmetic (dream2real_amd/csrc/tsdfvis_rect.h, d2r_shared.h's d2r_is_rigid) in a program of its own: tests/test_tsdfvis_host.py
 // builds it with -fsanitize=address,undefined and runs it.  Prints "ok" when every check holds.
 #include <stdio.h>
 
+#include "../dream2real_amd/csrc/d2r_shared.h"
 #include "../dream2real_amd/csrc/tsdfvis_rect.h"
 
 static int failures = 0;
@@ -27,22 +28,22 @@ static TvRect rect_of(const float m[12], const double lo[3], const double hi[3],
 int main()
 {
     float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    CHECK(tv_is_rigid(I));
+    CHECK(d2r_is_rigid(I));
     float T[16];
     for (int i = 0; i < 16; ++i) T[i] = I[i];
     T[0] = 1.01f;
-    CHECK(!tv_is_rigid(T));                  // scaled
+    CHECK(!d2r_is_rigid(T));                  // scaled
     T[0] = 1.0f;
     T[3] = INFINITY;
-    CHECK(!tv_is_rigid(T));                  // not finite
+    CHECK(!d2r_is_rigid(T));                  // not finite
     T[3] = 5.0f;
     T[15] = 2.0f;
-    CHECK(!tv_is_rigid(T));                  // last row
+    CHECK(!d2r_is_rigid(T));                  // last row
     T[15] = 1.0f;
     T[5] = T[10] = 0.0f;                     // a quarter turn about x
     T[6] = -1.0f;
     T[9] = 1.0f;
-    CHECK(tv_is_rigid(T));
+    CHECK(d2r_is_rigid(T));
 
     const double E[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     const double fx = 100, fy = 100, cx = 50, cy = 40, near = 0.01;
@@ -76,7 +77,7 @@ int main()
     CHECK(same(tv_box_rect(E, lo, hi, 0.0, 1e308, fy, cx, cy, near, W, H), 49, 29, W - 1, 41));
     // off by more than 1e-5 from orthogonal: refused (the rectangle and the rule invert by transposition)
     T[5] = 1e-4f;
-    CHECK(!tv_is_rigid(T));
+    CHECK(!d2r_is_rigid(T));
     // a rotated transform: the camera looks back along -z from z = 3
     const double B[16] = {-1, 0, 0, 0, 0, 1, 0, 0, 0, 0, -1, 3, 0, 0, 0, 1};
     CHECK(same(tv_box_rect(B, lo, hi, 0.0, fx, fy, cx, cy, near, W, H), 39, 29, 51, 41));

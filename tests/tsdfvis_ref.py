@@ -115,18 +115,10 @@ def _sample(vol, p, thr, box=None, gt=False):
     """p float32 [n,3] -> (observed bool [n], trilinear tsdf float32 [n], cell (x, y, z) local int64 [n] each, fractions [n,3], cell
     inside bool [n], global cell float32 [n,3]).  box = (clo, chi): the GPU's skip, restated: a cell outside clo .. chi, or whose own
     block no frame touched, is unobserved without a look at its weights.  gt restates a WRONG rule: weight > thr."""
-    lo = (vol.b0 * BLOCK).astype(np.float64)
-    hi = lo + vol.nv
-    with np.errstate(all="ignore"):
-        g = p / vol.voxel
-        c = np.floor(g)
-        fr = (g - c).astype(np.float32)
-        inside = np.ones(len(p), bool)
-        for a in range(3):
-            if box is None:
-                inside &= (c[:, a] >= lo[a]) & (c[:, a] + 1 <= hi[a] - 1)       # both corners along the axis lie in the grid
-            else:
-                inside &= (c[:, a] >= f32(box[0][a])) & (c[:, a] <= f32(box[1][a]))
+    lo = vol.b0 * BLOCK
+    clo, chi = (lo, lo + vol.nv - 2) if box is None else box      # no box: both corners along every axis lie in the grid
+    inside, c, fr = tsdf_ref.cell(p, vol.voxel, clo, chi)
+    inside = inside.all(axis=1)
     q = [np.where(inside, c[:, a], lo[a]).astype(np.int64) - int(lo[a]) for a in range(3)]
     t = [vol.tsdf[q[2] + (k >> 2), q[1] + ((k >> 1) & 1), q[0] + (k & 1)] for k in range(8)]
     ok = inside.copy()
@@ -135,21 +127,12 @@ def _sample(vol, p, thr, box=None, gt=False):
     for k in range(8):
         w = vol.w[q[2] + (k >> 2), q[1] + ((k >> 1) & 1), q[0] + (k & 1)]
         ok &= (w > f32(thr)) if gt else (w >= f32(thr))
-    return ok, _lerp3(t, fr), q, fr, inside, c
-
-
-def _lerp3(t, fr):
-    f0, f1, f2 = (fr[:, a] if t[0].ndim == 1 else fr[:, a:a + 1] for a in range(3))
-    with np.errstate(all="ignore"):
-        x00, x10 = t[0] + f0 * (t[1] - t[0]), t[2] + f0 * (t[3] - t[2])
-        x01, x11 = t[4] + f0 * (t[5] - t[4]), t[6] + f0 * (t[7] - t[6])
-        y0, y1 = x00 + f1 * (x10 - x00), x01 + f1 * (x11 - x01)
-        return y0 + f2 * (y1 - y0)
+    return ok, tsdf_ref.lerp3(t, fr), q, fr, inside, c
 
 
 def _colour_raw(vol, q, fr):
     t = [vol.col[q[2] + (k >> 2), q[1] + ((k >> 1) & 1), q[0] + (k & 1)] for k in range(8)]          # [n,3] each
-    return _lerp3(t, fr)
+    return tsdf_ref.lerp3(t, fr)
 
 
 def _round_colour(raw, wrong=frozenset()):
