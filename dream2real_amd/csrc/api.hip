@@ -149,14 +149,7 @@ struct Option {
     unsigned flags;
     int (*hook)(d2r_ctx *, int64_t value);  // optional, after the range check and before the store: a further check or a side effect
 };
-enum { OPT_DEV = 1,          // experiment switch of development builds (make DEV=1): schedules that were measured no faster and tile
-                             // configurations kept for comparison; a product build does not know the key
-       OPT_READ_ONLY = 2 };  // read-back of what the last launch ran with
-#ifdef D2R_DEV
-static const bool kDevBuild = true;
-#else
-static const bool kDevBuild = false;
-#endif
+enum { OPT_READ_ONLY = 1 };  // read-back of what the last launch ran with
 
 static int opt_march_threads(d2r_ctx *ctx, int64_t value)
 {
@@ -190,9 +183,6 @@ static const Option g_options[] = {
     {"march_threads", &d2r_ctx::march_threads, Option::RANGE, 0, D2R_MARCH_THREADS, 0, opt_march_threads},
     {"march_threads_auto_mib", &d2r_ctx::march_threads_auto_mib, Option::RANGE, 0, 1 << 20},
     {"march_blocks", &d2r_ctx::march_blocks, Option::RANGE, 0, 65535},
-    {"gemm_cfg", &d2r_ctx::gemm_cfg, Option::FREE, 0, 0, OPT_DEV},
-    {"gemm_group", &d2r_ctx::gemm_group, Option::RANGE, 0, 65535, OPT_DEV},
-    {"gemm_stagger", &d2r_ctx::gemm_stagger, Option::FLAG, 0, 0, OPT_DEV},
     {"gbrick_slots", &d2r_ctx::gbrick_slots, Option::RANGE, 0, 8},
     {"brick_slots_total", &d2r_ctx::brick_slots_total, Option::RANGE, 0, 8},
     {"lds_slots_max", &d2r_ctx::lds_slots_max, Option::RANGE, 0, 5},      // read by d2r_nerf_create: set it before creating the model
@@ -211,7 +201,7 @@ static const Option g_options[] = {
 static const Option *find_option(const char *key)
 {
     for (const Option &o : g_options)
-        if (!strcmp(key, o.key)) return (o.flags & OPT_DEV) && !kDevBuild ? nullptr : &o;
+        if (!strcmp(key, o.key)) return &o;
     return nullptr;
 }
 

@@ -1,7 +1,8 @@
 // clip_dev.h — measurement switches of clip.hip.  DEVELOPMENT BUILDS ONLY (make DEV=1, GEMM_ABLATE=<mask>, ATTN_ABLATE=<mask>,
 // or DEV=1 EXTRA=-DD2R_GEMM_STAMPS — the stamps need the development build): the product library is built with every
 // switch here off.  The Makefile keeps the flags of the last build in _build/flags.stamp, so changing any of them
-// rebuilds every object.
+// rebuilds every object.  Measurement instruments only: an alternative implementation whose A/B is decided does not
+// live here but in the history (docs/history/r27.md).
 //
 // D2R_GEMM_ABLATE (bitmask) — k_gemm8 and the shared epilogue: 1 no LDS-DMA, 2 no fragment ds_reads, 4 no epilogue,
 //   8 no MFMA, 128 no global loads/stores in the epilogue, 256 no LDS transposes in the epilogue.
@@ -23,11 +24,6 @@
 //   16 no MFMA, 32 no LDS-DMA, 64 no fragment reads.  Garbage results; tools/f8_ablate.sh.
 #ifndef D2R_F8_EXP
 #define D2R_F8_EXP 0
-#endif
-// D2R_F8_VAR (bitmask) — schedule variants of k_gemm8f's phase: 1 no s_setprio, 2 s_setprio 1 around the MFMA section of every wave (instead of
-//   a static priority for wave row 0), 4 staging requests before the fragment reads.  Same results.
-#ifndef D2R_F8_VAR
-#define D2R_F8_VAR 0
 #endif
 #ifdef D2R_GEMM_STAMPS
 #define D2R_GEMM_STAMP_KINDS 13          /* EPI_KINDS of clip.hip */

@@ -205,12 +205,9 @@ struct d2r_ctx {
                                // so a wave runs its 64 rays to the end (lane utilisation 0.79) rather than topping up at 16 free lanes (0.90)
     int64_t march_compact = 1; // marcher: compact a wave's last <= 32 rays into one tile (option "march_compact")
     int64_t ln_fold = 4;       // vision tower: 0 LayerNorm kernels + fp32 residual; LayerNorm folded into the GEMMs with 1 a split (hi + lo) bf16 residual, 2 a bf16 residual, 3 an fp32 residual + bf16 copy, 4 bf16 hi + one lo byte
-    int64_t gemm_stagger = 0;      // persistent GEMM: stagger the workgroups' first tile over a tile period (epilogues spread in time)
-    int64_t gemm_group = 65535;    // persistent GEMM: column tiles per group of the tile order (large = the plain column-fastest order, the default; 0 = the width a simple L2 model picks: a third fewer L2 misses, same time)
     int64_t gemm_nsplit = 0;     // column sections of the persistent GEMM's tile order (XCD sets own column ranges): 0 = two where the XCDs and the column tiles divide evenly, 1 = none
     int64_t attn_rem = 1;          // attention: a remainder of at most this many query tiles (sequence = 8 g + r tiles) runs on workgroups of r waves instead of one more eight-wave group
     int64_t cls_last = 1;          // vision tower: run the last block on the class-token rows only (the head reads nothing else)
-    int64_t gemm_cfg = 0;      // experiment switch for the GEMM tile configuration (0 = default)
     int64_t mlp_f16 = 1;       // operand type of the NeRF MLPs' MFMAs: 1 (default since round 6) fp16 — the reference's operand type (tiny-cuda-nn), the snapshot's weights unrounded; 0 bf16 (north_star's wording).  Same MFMA rate; chosen by the distance table of tests/test_gpu_parity.py::test_render_distances_to_the_fp16_accumulation_emulation
     int64_t render_arith = 0;  // arithmetic of the field evaluation (nerf.hip eval_wave<…, ARITH>): 0 the specification (fp32 accumulation); 1 / 2 oracle/d2r_oracle.c's d2r_oracle_set_arith(1 / 2) restated — hash-grid corners summed in half (2: the fma form), half accumulators in both MLPs (one rounding per 16-wide k-step), half activations.  A validation mode: brick-free kernels, fp16 operands whatever mlp_f16 says
     int64_t use_bricks = 1;

@@ -172,12 +172,6 @@ __global__ void k_cameras_virtual(ViewParams V, Mat16 obj_now, Mat16 cam, const 
 #ifndef D2R_MARCH_ABLATE
 #define D2R_MARCH_ABLATE 0            /* development: 1 no LDS-brick slots, 2 no global slots (HBM bricks / tables), 4 no MLPs, 8 no occupancy walk (fixed 16 samples per ray); wrong pixels, timing only */
 #endif
-#ifndef D2R_MARCH_VAR
-#define D2R_MARCH_VAR 0                /* bit 0: LDS-brick addresses formed in fp32 (slot_addr_lds_f); bit 1: the next lattice point's occupancy word requested before the field evaluation */
-#endif
-#ifndef D2R_MARCH_MLP2
-#define D2R_MARCH_MLP2 0               /* 1: both tiles of a wave iteration share every MLP weight fragment read (mlp_tile2) */
-#endif
 #ifndef D2R_MARCH_RESERVE
 #define D2R_MARCH_RESERVE 128          /* queue entries a wave reserves per atomic */
 #endif
@@ -428,27 +422,16 @@ __device__ __forceinline__ const uint64_t *occ_word_ptr(const NerfParams &P, con
 {
     return P.bricks + ((size_t)o.mip * 32768 + (o.cx >> 2) + 32 * ((o.cy >> 2) + 32 * (o.cz >> 2)));
 }
-// the occupancy word lattice point k will be tested against (D2R_MARCH_VAR & 2: requested one iteration ahead, before the field evaluation
-// of the current sample, so that its latency hides under the gathers and the MLP instead of heading the next iteration)
-template <bool CONE>
-__device__ __forceinline__ uint64_t occ_prefetch(const NerfParams &P, const Ray &r, uint32_t k)
-{
-    if (k > r.k_hi) return 0ull;
-    const OccCell o = occ_cell<CONE>(P, r, k);
-    return o.inside ? *occ_word_ptr(P, o) : 0ull;
-}
 
 // Advance k to the next lattice sample t0+k*dt that lies in an occupied cell.
 // Empty 4^3 bricks / empty cells are skipped conservatively (never past an untested
 // lattice point that could be in another cell).  Returns false when the ray is finished.
-// pre: optional, the occupancy word of lattice point k (occ_prefetch) — saves the first load.
 template <bool CONE>
 __device__ __forceinline__ bool next_sample(const NerfParams &P, const Ray &r, uint32_t &k, float &px,
-                                            float &py, float &pz, const uint64_t *pre = nullptr)
+                                            float &py, float &pz)
 {
     // approximate reciprocals are enough: they only size the conservative skip below
     float ix = __builtin_amdgcn_rcpf(r.dx), iy = __builtin_amdgcn_rcpf(r.dy), iz = __builtin_amdgcn_rcpf(r.dz);
-    bool first = pre != nullptr;
     while (k <= r.k_hi) {
         const OccCell o = occ_cell<CONE>(P, r, k);
         const float t = o.t;
@@ -456,10 +439,7 @@ __device__ __forceinline__ bool next_sample(const NerfParams &P, const Ray &r, u
         if (!o.inside) return false;
         const int mip = o.mip, cx = o.cx, cy = o.cy, cz = o.cz;
         const float cell = o.cell, corg = o.corg;
-        uint64_t w;
-        if (first) w = *pre;
-        else w = *occ_word_ptr(P, o);
-        first = false;
+        const uint64_t w = *occ_word_ptr(P, o);
         uint32_t bit = (cx & 3) + 4 * (cy & 3) + 16 * (cz & 3);
         if ((w >> bit) & 1ull) return true;
         // skip: to the far face of the empty brick, or of the empty cell (box units: cell size `cell`, origin `corg`)
@@ -848,30 +828,6 @@ __device__ __forceinline__ void slot_addr(const NerfParams &P, int slot, bool hi
     }
 }
 
-// LDS-brick slot, addresses formed in fp32 (D2R_MARCH_VAR & 1; same bits as slot_addr<K_BRICK>): w = fract(p), floor = p - w (exact),
-// byte offset = fma(gz, 4 nxy, fma(gy, 4 nx, fma(gx, 4, 4 base))) — integers below 2^24 (an LDS brick is < 2^18 bytes, a coordinate
-// < 2^12), so every step is exact — and ONE v_cvt_u32_f32 per (y, z) corner pair: no quarter-rate v_mul_lo_u32, no v_floor + v_cvt
-// per axis.  The strides live in registers as floats INSTEAD of the integers (round 4 kept both and spilled).
-// off4[j] = byte offset of the corner pair (x, x + 1) at (y + (j & 1), z + (j >> 1)).
-__device__ __forceinline__ void slot_addr_lds_f(const NerfParams &P, int slot, bool hi, float x, float y, float z, uint32_t *off4, float *w)
-{
-    const SlotMeta &m = P.slot[slot];
-    const float scale = hi ? m.scale[1] : m.scale[0];
-    const float nx4 = 4.0f * (float)(hi ? m.bnx[1] : m.bnx[0]), nxy4 = 4.0f * (float)(hi ? m.bnxy[1] : m.bnxy[0]);
-    const float base4 = 4.0f * (float)(hi ? m.bbase[1] : m.bbase[0]);
-    const float p0 = fmaf(scale, x, 0.5f), p1 = fmaf(scale, y, 0.5f), p2 = fmaf(scale, z, 0.5f);
-    w[0] = __builtin_amdgcn_fractf(p0);
-    w[1] = __builtin_amdgcn_fractf(p1);
-    w[2] = __builtin_amdgcn_fractf(p2);
-    const float gx = p0 - w[0], gy = p1 - w[1], gz = p2 - w[2];
-    const float b00 = fmaf(gz, nxy4, fmaf(gy, nx4, fmaf(gx, 4.0f, base4)));
-    const float b10 = b00 + nx4, b01 = b00 + nxy4, b11 = b10 + nxy4;
-    off4[0] = (uint32_t)b00;
-    off4[1] = (uint32_t)b10;
-    off4[2] = (uint32_t)b01;
-    off4[3] = (uint32_t)b11;
-}
-
 // trilinear blend of the 8 corner entries, corner weights in the oracle's order ((wx*wy)*wz).
 // v_fma_mix_f32 multiplies the fp32 weight with one half of the packed fp16 pair and accumulates
 // in fp32 directly — no fp16->fp32 converts (hipcc does not form it with fp32 denormals on).
@@ -1030,16 +986,6 @@ __device__ __forceinline__ void encode_sample(const NerfParams &P, const __amdgp
         for (int i = 0; i < NB; i++) {
             uint32_t br[8];
             float bw[3];
-#if (D2R_MARCH_VAR & 1)
-            uint32_t bo4[4];
-            slot_addr_lds_f(P, i, hi, x, y, z, bo4, bw);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t *p = (const uint32_t *)(lds_bricks + bo4[j]);
-                br[2 * j] = p[0];
-                br[2 * j + 1] = p[1];
-            }
-#else
             uint32_t bo[8];
             slot_addr<K_BRICK>(P, i, hi, x, y, z, bo, bw);
 #pragma unroll
@@ -1048,7 +994,6 @@ __device__ __forceinline__ void encode_sample(const NerfParams &P, const __amdgp
                 br[2 * j] = p[0];
                 br[2 * j + 1] = p[1];
             }
-#endif
             slot_blend_as<ARITH>(br, bw, f[2 * i], f[2 * i + 1]);
         }
     };
@@ -1171,67 +1116,6 @@ __device__ __forceinline__ void mlp_tile(const uint4 *__restrict__ sw, uint32_t 
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// Both tiles of a wave iteration through both MLPs at once: every weight fragment is read from LDS ONCE and feeds two
-// independent MFMAs (tile A, tile B), so the 48 KiB of fragment reads per wave iteration become 24 KiB and each layer is
-// two interleaved dependent chains instead of one.  Per-sample arithmetic is mlp_tile's, operation by operation.
-template <bool F16>
-__device__ __forceinline__ void mlp_tile2(const uint4 *__restrict__ sw, uint32_t lane, const uint4 &a0, const uint4 &a1, const uint4 &shA, float *outA,
-                                          const uint4 &b0, const uint4 &b1, const uint4 &shB, float *outB)
-{
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // one 32-output half of a layer for both tiles: NK weight fragments starting at sw[W0], inputs xa[] / xb[]; the halves run one after
-    // the other with a scheduling fence in between so that ONE accumulator per tile is live beside the packed activations
-    // (both halves at once, four accumulators, pushed 37 registers of ray state to scratch)
-    auto half2 = [&](int W0, int NK, const uint4 *xa, const uint4 *xb, f32x16 &ra, f32x16 &rb) {
-        uint4 w = sw[W0 * 64 + lane];
-        ra = mfma<F16>(w, xa[0], zero);
-        rb = mfma<F16>(w, xb[0], zero);
-#pragma unroll
-        for (int i = 1; i < NK; i++) {
-            w = sw[(W0 + i) * 64 + lane];
-            ra = mfma<F16>(w, xa[i], ra);
-            rb = mfma<F16>(w, xb[i], rb);
-        }
-    };
-    f32x16 g, k;
-    uint4 pa[4], pb[4], xa[4], xb[4];
-    // density layer 1: 64 x 32
-    xa[0] = a0; xa[1] = a1; xb[0] = b0; xb[1] = b1;
-    half2(0, 2, xa, xb, g, k);
-    pa[0] = relu_pack<F16>(g, 0); pa[1] = relu_pack<F16>(g, 8); pb[0] = relu_pack<F16>(k, 0); pb[1] = relu_pack<F16>(k, 8);
-    __builtin_amdgcn_sched_barrier(0);
-    half2(2, 2, xa, xb, g, k);
-    pa[2] = relu_pack<F16>(g, 0); pa[3] = relu_pack<F16>(g, 8); pb[2] = relu_pack<F16>(k, 0); pb[3] = relu_pack<F16>(k, 8);
-    __builtin_amdgcn_sched_barrier(0);
-    // density layer 2: 16 (padded 32) x 64
-    half2(4, 4, pa, pb, g, k);
-    outA[0] = g[0];
-    outB[0] = k[0];
-    // colour layer 1: 64 x 32, input = [density out (no activation) | SH]
-    xa[0].x = pack2<F16>(g[0], g[1]); xa[0].y = pack2<F16>(g[2], g[3]); xa[0].z = pack2<F16>(g[4], g[5]); xa[0].w = pack2<F16>(g[6], g[7]);
-    xb[0].x = pack2<F16>(k[0], k[1]); xb[0].y = pack2<F16>(k[2], k[3]); xb[0].z = pack2<F16>(k[4], k[5]); xb[0].w = pack2<F16>(k[6], k[7]);
-    xa[1] = shA; xb[1] = shB;
-    __builtin_amdgcn_sched_barrier(0);
-    half2(8, 2, xa, xb, g, k);
-    pa[0] = relu_pack<F16>(g, 0); pa[1] = relu_pack<F16>(g, 8); pb[0] = relu_pack<F16>(k, 0); pb[1] = relu_pack<F16>(k, 8);
-    __builtin_amdgcn_sched_barrier(0);
-    half2(10, 2, xa, xb, g, k);
-    pa[2] = relu_pack<F16>(g, 0); pa[3] = relu_pack<F16>(g, 8); pb[2] = relu_pack<F16>(k, 0); pb[3] = relu_pack<F16>(k, 8);
-    __builtin_amdgcn_sched_barrier(0);
-    // colour layer 2: 64 x 64
-    half2(12, 4, pa, pb, g, k);
-    xa[0] = relu_pack<F16>(g, 0); xa[1] = relu_pack<F16>(g, 8); xb[0] = relu_pack<F16>(k, 0); xb[1] = relu_pack<F16>(k, 8);
-    __builtin_amdgcn_sched_barrier(0);
-    half2(16, 4, pa, pb, g, k);
-    xa[2] = relu_pack<F16>(g, 0); xa[3] = relu_pack<F16>(g, 8); xb[2] = relu_pack<F16>(k, 0); xb[3] = relu_pack<F16>(k, 8);
-    __builtin_amdgcn_sched_barrier(0);
-    // colour layer 3: 16 (padded 32) x 64
-    half2(20, 4, xa, xb, g, k);
-    outA[1] = g[0]; outA[2] = g[1]; outA[3] = g[2];
-    outB[1] = k[0]; outB[2] = k[1]; outB[3] = k[2];
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // One tile through both MLPs with HALF accumulators (option "render_arith" 1 / 2; oracle/d2r_oracle.c matvec_f16_halfacc / nerf_eval):
 // one v_mfma_f32_32x32x16_f16 has K = 16, so one MFMA from a ZERO accumulator is one 16-wide k-step's sum of exact products (the
 // oracle's `part`); a VALU add and a convert round it into the running half accumulator, acc = rn16(acc + part).  The fragment order
@@ -1347,14 +1231,8 @@ __device__ __forceinline__ void eval_wave(const NerfParams &P, const __amdgpu_bu
         if ((uint32_t)vm != 0u) mlp_tile_half(sw, lane, fa0, fa1, shfA, oa);
         if ((uint32_t)(vm >> 32) != 0u) mlp_tile_half(sw, lane, fb0, fb1, shfB, ob);
     } else {
-#if D2R_MARCH_MLP2
-    if ((uint32_t)vm != 0u && (uint32_t)(vm >> 32) != 0u) mlp_tile2<F16>(sw, lane, fa0, fa1, shfA, oa, fb0, fb1, shfB, ob);
-    else if ((uint32_t)vm != 0u) mlp_tile<F16>(sw, lane, fa0, fa1, shfA, oa);
-    else if ((uint32_t)(vm >> 32) != 0u) mlp_tile<F16>(sw, lane, fb0, fb1, shfB, ob);
-#else
     if ((uint32_t)vm != 0u) mlp_tile<F16>(sw, lane, fa0, fa1, shfA, oa);
     if ((uint32_t)(vm >> 32) != 0u) mlp_tile<F16>(sw, lane, fb0, fb1, shfB, ob);
-#endif
     }
 #endif
     // tile-1 results live in lanes 0..31; their owners are lanes 32..63
@@ -1535,10 +1413,6 @@ __global__ __launch_bounds__(D2R_MARCH_THREADS) void k_march(NerfParams P, ViewP
         }
 #endif
 
-#if (D2R_MARCH_VAR & 2)
-        uint64_t occ_next = 0ull;
-        if (alive) occ_next = occ_prefetch<CONE>(P, ray, k + 1);
-#endif
         // ---- evaluate this wave's samples
         float sigma, cr, cg, cb;
         eval_wave<NB, NGB, ND, F16, ARITH>(P, rs, rsb, sw, lds_bricks, lane, alive, px, py, pz, shfA, shfB, sigma, cr, cg, cb);
@@ -1564,11 +1438,7 @@ __global__ __launch_bounds__(D2R_MARCH_THREADS) void k_march(NerfParams P, ViewP
                 done = true;
             } else {
                 k++;
-#if (D2R_MARCH_VAR & 2)
-                done = !next_sample<CONE>(P, ray, k, px, py, pz, &occ_next);
-#else
                 done = !next_sample<CONE>(P, ray, k, px, py, pz);
-#endif
             }
             if (done) {
                 alive = false;
