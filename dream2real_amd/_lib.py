@@ -112,6 +112,9 @@ PROTOTYPES = {
     "d2r_thumbs_get_timing": (_int, (_ptr, _ptr)),
     "d2r_proposals_labels": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr)),
     "d2r_proposals_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_labeltrack_grid": (_int, (_ptr, _ptr, _ptr, _ptr)),
+    "d2r_labeltrack_scan": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_labeltrack_get_timing": (_int, (_ptr, _ptr)),
 }
 EXPORTS = list(PROTOTYPES)
 

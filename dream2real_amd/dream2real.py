@@ -196,7 +196,10 @@ class ImaginationEngine:
             raise ValueError("ImaginationEngine: proposer= and tracker= come together, " +
                              ("tracker=" if tracker is None else "proposer=") + " is missing")
         # proposer: callable(uint8 [W,H,3], frame 0 turned upright) -> bool [M,W,H] mask proposals (SAM's mask generator alone);
-        # tracker: callable(rgbs, labels0 uint8 [H,W]) -> uint8 [N,H,W] raw label images (XMem alone)
+        # tracker: callable(rgbs, labels0 uint8 [H,W]) -> uint8 [N,H,W] raw label images (XMem alone), or "geometric": the labels
+        # are carried through the scan by depth and pose on the GPU (segmentation.track_labels)
+        if isinstance(tracker, str) and tracker != "geometric":
+            raise ValueError(f"ImaginationEngine: tracker= is a callable or \"geometric\", got {tracker!r}")
         self.proposer, self.tracker = proposer, tracker
         if intrinsics is None:
             from .scene import INTRINSICS_REALSENSE_1280
@@ -247,7 +250,11 @@ class ImaginationEngine:
             first = np.rot90(rgbs_np[0], 1)
             inside = np.rot90(_np(self.out_scene_bound_masks[0]) == 0)
             labels0 = np.rot90(segmentation.proposals_to_labels(self.proposer(first), inside, ctx=self.ctx), 3)
-            raw_masks = np.asarray(_np(self.tracker(rgbs, np.ascontiguousarray(labels0))), np.uint8)
+            if isinstance(self.tracker, str):              # "geometric"
+                raw_masks = segmentation.track_labels(depths, loader.T_WC_data, intrinsics, np.ascontiguousarray(labels0),
+                                                      cfg.scene_phys_bounds, ctx=self.ctx)
+            else:
+                raw_masks = np.asarray(_np(self.tracker(rgbs, np.ascontiguousarray(labels0))), np.uint8)
             if raw_masks.shape != rgbs_np.shape[:3]:
                 raise ValueError(f"tracker returned label images of shape {raw_masks.shape}, expected {rgbs_np.shape[:3]}")
             masks = segmentation.refine_masks(raw_masks, depths, loader.T_WC_data, intrinsics, self.out_scene_bound_masks,

@@ -5,9 +5,11 @@ is DESIGN.md section 2d.
 
 Running SAM or XMem is out of scope: `proposals_to_labels` turns the mask generator's proposals into the first frame's label
 image (sam_seg.py:80-115 and integrate_masks); whatever produced the raw label images of all frames (XMem in
-the reference), `refine_masks` is the body of the `segment_associate` loop from there on and `load_cached_masks` its cache branch."""
+the reference), `refine_masks` is the body of the `segment_associate` loop from there on and `load_cached_masks` its cache branch.
+`track_labels` is this package's own way from the first label image to all of them: by geometry, on the GPU."""
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import numpy as np
@@ -85,6 +87,68 @@ def proposals_to_labels(proposals, inside=None, *, ctx, return_records=False):
         return out
     labels, recs = out
     return labels, np.ascontiguousarray(recs).view(PROPOSAL_RECORD).reshape(-1)
+
+
+# the mirror of include/d2r.h's d2r_labeltrack_params (tests/test_labeltrack_host.py holds its layout to a C compiler's)
+class LabeltrackParams(C.Structure):
+    _fields_ = [("voxel", C.c_float), ("band_voxels", C.c_uint32), ("tau_mm", C.c_uint32), ("grow", C.c_uint32)]
+
+
+def _labeltrack_bounds(scene_bounds):
+    b = np.ascontiguousarray(np.asarray(_np(scene_bounds), np.float64).reshape(-1))
+    if b.size != 6:
+        raise ValueError(f"scene_bounds must be [[min xyz], [max xyz]], got {b.size} numbers")
+    return b
+
+
+def labeltrack_grid(scene_bounds, voxel=0.004, band_voxels=2):
+    """d2r_labeltrack_grid (host only): the grid track_labels lays over scene_bounds -> (dims uint32 [3] along x, y, z, lo int32 [3])."""
+    params = LabeltrackParams(float(voxel), int(band_voxels), 0, 0)
+    dims, lo = np.zeros(3, np.uint32), np.zeros(3, np.int32)
+    _lib.check(_lib.load().d2r_labeltrack_grid(_lib.ptr(_labeltrack_bounds(scene_bounds)), C.byref(params), _lib.ptr(dims), _lib.ptr(lo)))
+    return dims, lo
+
+
+def track_labels(depths, cam_poses, intrinsics, labels0, scene_bounds, *, ctx, voxel=0.004, band_voxels=2, tau_mm=10, grow=64,
+                 return_stats=False, return_volume=False):
+    """The first frame's label image carried to every frame of a scan by geometry (d2r_labeltrack_scan): a
+    voxel grid over scene_bounds holds a (label, count) pair per voxel; frame 0 votes labels0 into it; every later frame, in order,
+    reads its labels from the grid, grows them along depth-continuous image paths (`grow` sweeps, a step of more than tau_mm
+    millimetres is not crossed) and votes in turn.  depths [N,H,W] metres (or uint16 millimetres), cam_poses [N,4,4] camera to
+    world, intrinsics [3,3], labels0 uint8 [H,W] without 255 -> uint8 [N,H,W], frame 0's being labels0; pixels the labels did not
+    reach are 0.  return_stats: also uint32 [N,4] (known after the prediction, labelled by the fill, left unknown, fill launches that
+    changed a pixel); return_volume: also (uint16 [nz,ny,nx] label | count << 8, dims, lo)."""
+    d = depth_to_u16(np.stack([_np(x) for x in depths]) if isinstance(depths, (list, tuple)) else depths)
+    if d.ndim != 3:
+        raise ValueError(f"depths must be [N, H, W], got shape {d.shape}")
+    n, h, w = d.shape
+    T = np.ascontiguousarray(np.array([np.asarray(_np(p), np.float64).reshape(16) for p in cam_poses]), np.float32)
+    if T.shape != (n, 16):
+        raise ValueError(f"{T.shape[0]} poses for {n} frames")
+    K = np.asarray(_np(intrinsics), np.float64).reshape(3, 3)
+    K4 = np.ascontiguousarray([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float64)
+    l0 = np.ascontiguousarray(_np(labels0), np.uint8)
+    if l0.shape != (h, w):
+        raise ValueError(f"labels0 must be [H, W] = {(h, w)}, got shape {l0.shape}")
+    b = _labeltrack_bounds(scene_bounds)
+    params = LabeltrackParams(float(voxel), int(band_voxels), int(tau_mm), int(grow))
+    out = np.zeros((n, h, w), np.uint8)
+    stats = np.zeros((n, 4), np.uint32) if return_stats else None
+    vol = dims = lo = None
+    if return_volume:
+        dims, lo = labeltrack_grid(b, voxel, band_voxels)
+        vol = np.zeros((int(dims[2]), int(dims[1]), int(dims[0])), np.uint16)
+    ctx.check(ctx.lib.d2r_labeltrack_scan(ctx.h, _lib.ptr(b), C.byref(params), n, w, h, _lib.ptr(K4), _lib.ptr(d), _lib.ptr(T), _lib.ptr(l0),
+                                          _lib.ptr(out), _lib.ptr(stats), _lib.ptr(vol), _lib.ptr(dims), _lib.ptr(lo)))
+    res = (out,) + ((stats,) if return_stats else ()) + (((vol, dims, lo),) if return_volume else ())
+    return res if len(res) > 1 else out
+
+
+def labeltrack_timing(ctx):
+    """d2r_labeltrack_get_timing -> (upload, kernels, download) of the context's last track_labels, device-event milliseconds."""
+    ms = np.zeros(3, np.float64)
+    ctx.check(ctx.lib.d2r_labeltrack_get_timing(ctx.h, _lib.ptr(ms)))
+    return tuple(float(x) for x in ms)
 
 
 def labels_from_census(counts):

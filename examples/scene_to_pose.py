@@ -1,5 +1,5 @@
 """A scan folder and a settings file in, the best pose out: the three calls of ImaginationEngine.
-    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--vis-backend tsdf] [--refine-poses] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy]
+    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--vis-backend tsdf] [--refine-poses] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy | --proposals FILE.npy --geometric-tracker]
 --vis also writes best_pose_vis.png (and, without use_vis_pcds, cost_volume.png) into the folder.
 --vis-backend tsdf renders the candidates from colour-TSDF volumes fused from the scan instead of the settings
 file's visual model (NeRF snapshots, or point clouds with use_vis_pcds, which it switches off).
@@ -9,6 +9,8 @@ file's visual model (NeRF snapshots, or point clouds with use_vis_pcds, which it
 --proposals FILE.npy --tracked FILE.npy stand in for the two segmentation models: the mask generator's recorded proposals, bool [M,W,H]
 for the first frame turned upright, and the tracker's recorded raw label images, uint8 [N,H,W]; the engine builds the first label image
 between them instead of reading XMem_masks/.
+--geometric-tracker in place of --tracked: the first label image is carried through the scan by depth and pose on the GPU (DESIGN.md
+section 2k), no tracking network and no recording of one.
 The folder holds poses.txt, images/, depth/, XMem_masks/ (use_cache_segs), captions.json and lang_cache.json (a
 CachedLangModel file); clip_dir holds a CLIP checkpoint: model.safetensors, vocab.json, merges.txt."""
 import os
@@ -41,15 +43,21 @@ for flag in ("--proposals", "--tracked"):
         at = argv.index(flag)
         recorded[flag] = argv[at + 1]
         del argv[at:at + 2]
-if len(recorded) == 1:
-    sys.exit("--proposals and --tracked come together")
+geometric = "--geometric-tracker" in argv
+if geometric:
+    argv.remove("--geometric-tracker")
+if geometric and "--tracked" in recorded:
+    sys.exit("--geometric-tracker stands in place of --tracked")
+if ("--proposals" in recorded) != (geometric or "--tracked" in recorded):
+    sys.exit("--proposals comes with --tracked or --geometric-tracker")
 vis = "--vis" in argv
 config_file, data_dir, user_instr, clip_dir = [a for a in argv if a != "--vis"][:4]
 cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=not recorded, phys_backend="tsdf", **backend)
 models = {}
 if recorded:
     import numpy as np
-    models = dict(proposer=lambda image: np.load(recorded["--proposals"]), tracker=lambda frames, labels0: np.load(recorded["--tracked"]))
+    models = dict(proposer=lambda image: np.load(recorded["--proposals"]),
+                  tracker="geometric" if geometric else lambda frames, labels0: np.load(recorded["--tracked"]))
 ctx = engine.Context(0)
 clip_cfg, state = load_clip_safetensors(os.path.join(clip_dir, "model.safetensors"))
 imagination = ImaginationEngine(cfg, ctx, engine.ClipScorer(ctx, clip_cfg, state),

@@ -1012,6 +1012,50 @@ D2R_API int d2r_proposals_labels(d2r_ctx *ctx, const uint8_t *props_u8, const ui
  * milliseconds. */
 D2R_API int d2r_proposals_get_timing(d2r_ctx *ctx, double *ms_out);
 
+/* ------------------------------------------------- first-frame labels carried through a scan by geometry (tracker="geometric")
+ *
+ * This package's own stand-in for the video-object-segmentation network (XMem) the reference tracks its first label image with; nothing
+ * here stands where reference code stands.  A scan is a static scene seen from known poses with metric depth: a voxel grid over the
+ * scene bounds holds one (label, count) pair per voxel.  Frame 0 votes its label image into the grid; every later frame, in order,
+ * reads a label per pixel from the voxel its depth back-projects to (predict), grows the known labels into the unknown pixels along
+ * depth-continuous 4-neighbour paths for `grow` Jacobi sweeps (fill), is written out with the unknown pixels as 0, and votes what it
+ * holds into the grid (Boyer-Moore majority, one lane per voxel, no atomics).  fp32 arithmetic, one IEEE operation at a time.
+ */
+#define D2R_LABELTRACK_UNKNOWN 255u        /* inside the unit only: never in labels0, never in labels_out */
+#define D2R_LABELTRACK_SWEEPS_PER_LAUNCH 8u /* the sweeps one fill launch runs: the unit of stats_out's last column */
+#define D2R_LABELTRACK_MAX_PIXELS (1u << 21)
+#define D2R_LABELTRACK_MAX_VOXELS (1ull << 31)
+#define D2R_LABELTRACK_MAX_COORD (1 << 23)  /* |voxel coordinate| of the grid's faces: every one is an exact float */
+
+typedef struct d2r_labeltrack_params {
+    float voxel;              /* metres, finite, > 0; 0.004 by default in the Python layer */
+    uint32_t band_voxels;     /* 1 .. 8: the grid's padding and the vote's depth band, in voxels; 2 */
+    uint32_t tau_mm;          /* 0 .. 65535: the largest depth step a label crosses in the fill, millimetres; 10 */
+    uint32_t grow;            /* 0 .. 4096: sweeps of the fill; 64 */
+} d2r_labeltrack_params;
+
+/* The grid d2r_labeltrack_scan lays over bounds (host [6]: xmin ymin zmin xmax ymax zmax): dims_out host [3] voxels along x, y, z,
+ * lo_out host [3] the first voxel's coordinate per axis; vol_out of the scan holds dims[0] * dims[1] * dims[2] uint16.  Host only.
+ * Refused with D2R_ERR_INVALID, outputs untouched: null arguments, a parameter outside its range, non-finite or inverted bounds,
+ * a face beyond D2R_LABELTRACK_MAX_COORD voxels from the origin, more than D2R_LABELTRACK_MAX_VOXELS voxels. */
+D2R_API int d2r_labeltrack_grid(const double *bounds, const d2r_labeltrack_params *params, uint32_t *dims_out, int32_t *lo_out);
+
+/* d16 host [n][h][w] millimetres, cam_poses host [n][16] fp32 row-major camera-to-world (OpenCV), K host [4]: fx fy cx cy,
+ * labels0 host [h][w] frame 0's labels (0 the background, 255 refused).  labels_out host [n][h][w]: frame 0's is labels0.
+ * stats_out (optional) host [n][4]: pixels known after predict, pixels the fill labelled, pixels left unknown, fill launches (of
+ * D2R_LABELTRACK_SWEEPS_PER_LAUNCH sweeps) in which a pixel changed; frame 0's row is w h, 0, 0, 0.  vol_out (optional) host
+ * [dims z][dims y][dims x] uint16, label in the low byte and count in the high byte, after the last frame's vote; vol_dims_out and
+ * vol_lo_out (optional) host [3] as d2r_labeltrack_grid gives them.  Refused with D2R_ERR_INVALID before any device work, outputs
+ * untouched: what d2r_labeltrack_grid refuses, null arguments, n = 0, w h = 0 or above D2R_LABELTRACK_MAX_PIXELS, a non-rigid (R^T R = I
+ * to 1e-5, last row 0 0 0 1) or non-finite pose, non-finite intrinsics or a zero focal length, a 255 in labels0.  All frames are
+ * uploaded once; no host synchronisation between the frames.  Synchronous. */
+D2R_API int d2r_labeltrack_scan(d2r_ctx *ctx, const double *bounds, const d2r_labeltrack_params *params, uint32_t n, uint32_t w, uint32_t h,
+                                const double *K, const uint16_t *d16, const float *cam_poses, const uint8_t *labels0, uint8_t *labels_out,
+                                uint32_t *stats_out, uint16_t *vol_out, uint32_t *vol_dims_out, int32_t *vol_lo_out);
+
+/* Device-event times of the context's last d2r_labeltrack_scan: ms_out host [3] = upload, kernels, download, in milliseconds. */
+D2R_API int d2r_labeltrack_get_timing(d2r_ctx *ctx, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif
