@@ -115,6 +115,8 @@ PROTOTYPES = {
     "d2r_labeltrack_grid": (_int, (_ptr, _ptr, _ptr, _ptr)),
     "d2r_labeltrack_scan": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
     "d2r_labeltrack_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_geoprop_masks": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_geoprop_get_timing": (_int, (_ptr, _ptr)),
 }
 EXPORTS = list(PROTOTYPES)
 

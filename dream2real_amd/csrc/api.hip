@@ -303,7 +303,7 @@ void d2r_ctx_destroy(d2r_ctx *c)
                             &c->text, &c->logits, &c->pix, &c->bg_rgba, &c->bg_depth, &c->bg_u8, &c->rects, &c->bg_patches, &c->rect_ws, &c->lens_tab,
                             &c->patches2, &c->frames2, &c->bg_l0, &c->l0_a1, &c->l0_q2, &c->l0_misc,
                             &c->pcd_mats, &c->pcd_bg_keys, &c->pcd_bg_frame, &c->pcd_cols,
-                            &c->tv_mats, &c->tv_bg_frame, &c->tv_bg_depth, &c->tv_depth, &c->ct_in, &c->ct_ws, &c->lt_in, &c->lt_ws,
+                            &c->tv_mats, &c->tv_bg_frame, &c->tv_bg_depth, &c->tv_depth, &c->ct_in, &c->ct_ws, &c->lt_in, &c->lt_ws, &c->gp_in, &c->gp_ws,
                             &c->mv_in, &c->mv_recs, &c->mv_queue, &c->mv_shade, &c->mv_keys, &c->mv_out,
                             &c->mask_in, &c->mask_out, &c->mask_ws, &c->thumb_in, &c->thumb_ws, &c->thumb_out,
                             &c->prop_in, &c->prop_ws, &c->prop_out};

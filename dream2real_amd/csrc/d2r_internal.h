@@ -149,6 +149,8 @@ struct d2r_ctx {
     bool ct_timed = false;
     Buf lt_in, lt_ws;            // labeltrack.hip: the uploaded depth frames + first label image + per-frame matrices (one D2rStage), the two label planes + result frames + counters
     D2rStageTimer lt_timer;      // ... upload / kernels / download of the last d2r_labeltrack_scan (d2r_labeltrack_get_timing)
+    Buf gp_in, gp_ws;            // geoprop.hip: the uploaded depth frame, height bins / histogram / link planes / union-find parents / statistics / candidates / label image (one D2rStage)
+    D2rStageTimer gp_timer, gp_timer2;   // ... upload / heights / components, then selection / download of the last d2r_geoprop_masks (d2r_geoprop_get_timing)
     Buf mv_in, mv_recs, mv_queue, mv_shade, mv_keys, mv_out;   // meshvis.hip: uploaded inputs (seven segments of a D2rStage), triangle records, the large-triangle queue, shade bytes, mesh + cube key buffers, rgb + ids of the current call
     Buf mask_in, mask_out, mask_ws;   // masks.hip: uploaded frames + per-label slots (the segments of a D2rStage per entry point), result frames, union-find parents + component statistics of a pass
     Buf thumb_in, thumb_ws, thumb_out;   // masks.hip, object thumbnails: frames + noise + records (one D2rStage), statistics / labelling / blur workspace, the packed thumbnails

@@ -166,10 +166,13 @@ __device__ inline void uf_unite(uint32_t *par, uint32_t a, uint32_t b)
 // ------------------------------------------------------------------------------------------------ component labelling
 // 8-connected components of equal non-zero label: parent[g] of a labelled pixel ends as the smallest raster index of its component
 // (pixels of label 0 are left alone: every reader tests the label first).  A pixel source gives the tile staging in LDS with the
-// "equal, non-zero label" test between two tile positions, and the label at (frame, i, j) from global memory.
+// "equal, non-zero label" test between two tile positions, and the label at (frame, i, j) from global memory.  Its CONN is 8, or 4
+// for a source whose test is a link between a pixel and its left or upper neighbour (geoprop.hip's LinkSrc): the labeller then
+// visits no diagonal, and `same`, `left` and `up` are asked about those two neighbours alone.
 
 // byte label images [frames][H][W]: the value is the label
 struct ByteSrc {
+    static constexpr int CONN = 8;
     const uint8_t *img;
     int W, H;
     struct Tile {
@@ -184,10 +187,14 @@ struct ByteSrc {
     }
     __device__ static bool same(const Tile &t, int q, int n) { return t.lab[q] && t.lab[q] == t.lab[n]; }
     __device__ uint8_t at(uint32_t frame, int i, int j) const { return img[(size_t)frame * W * H + (size_t)i * W + j]; }
+    // (i, j) of label l joins its left / upper neighbour
+    __device__ bool left(uint32_t frame, uint8_t l, int i, int j) const { return at(frame, i, j - 1) == l; }
+    __device__ bool up(uint32_t frame, uint8_t l, int i, int j) const { return at(frame, i - 1, j) == l; }
 };
 
 // bit planes [planes][H][WW], the tail bits of a row's last word 0: the value is 0 or 1, a tile is one word of LB_TH rows
 struct BitSrc {
+    static constexpr int CONN = 8;
     const unsigned long long *bits;
     int W, H, WW;
     struct Tile {
@@ -200,6 +207,8 @@ struct BitSrc {
     }
     __device__ static bool same(const Tile &t, int q, int n) { return (t.row[q / LB_TW] >> (q % LB_TW)) & (t.row[n / LB_TW] >> (n % LB_TW)) & 1ull; }
     __device__ uint8_t at(uint32_t frame, int i, int j) const { return plane_bit(bits + (size_t)frame * H * WW, WW, i, j); }
+    __device__ bool left(uint32_t frame, uint8_t l, int i, int j) const { return at(frame, i, j - 1) == l; }
+    __device__ bool up(uint32_t frame, uint8_t l, int i, int j) const { return at(frame, i - 1, j) == l; }
 };
 
 // parent[g] = raster index of the smallest pixel of g's component INSIDE its tile
@@ -217,9 +226,11 @@ __global__ __launch_bounds__(MK_THREADS) void k_label_tiles(Src src, uint32_t *_
         if (!Src::same(tile, q, q)) continue;
         if (c > 0 && Src::same(tile, q, q - 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - 1));
         if (r > 0) {
-            if (c > 0 && Src::same(tile, q, q - LB_TW - 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW - 1));
+            if constexpr (Src::CONN == 8)
+                if (c > 0 && Src::same(tile, q, q - LB_TW - 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW - 1));
             if (Src::same(tile, q, q - LB_TW)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW));
-            if (c + 1 < LB_TW && Src::same(tile, q, q - LB_TW + 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW + 1));
+            if constexpr (Src::CONN == 8)
+                if (c + 1 < LB_TW && Src::same(tile, q, q - LB_TW + 1)) uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, (uint32_t)q, (uint32_t)(q - LB_TW + 1));
         }
     }
     __syncthreads();
@@ -233,7 +244,7 @@ __global__ __launch_bounds__(MK_THREADS) void k_label_tiles(Src src, uint32_t *_
     }
 }
 
-// pixels on a tile border meet their W / NW / N / NE neighbours of equal label in the neighbouring tiles
+// pixels on a tile border meet their W / NW / N / NE neighbours of equal label in the neighbouring tiles (CONN 4: W and N alone)
 template <class Src>
 __global__ __launch_bounds__(MK_THREADS) void k_label_seams(Src src, uint32_t *__restrict__ parent)
 {
@@ -246,11 +257,13 @@ __global__ __launch_bounds__(MK_THREADS) void k_label_seams(Src src, uint32_t *_
     uint32_t *par = parent + (size_t)f * W * H;
     const uint8_t l = src.at(f, i, j);
     if (!l) return;
-    if (left && j > 0 && src.at(f, i, j - 1) == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - 1);
+    if (left && j > 0 && src.left(f, l, i, j)) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - 1);
     if (i > 0) {
-        if ((top || left) && j > 0 && src.at(f, i - 1, j - 1) == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W - 1);
-        if (top && src.at(f, i - 1, j) == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W);
-        if ((top || right) && j + 1 < W && src.at(f, i - 1, j + 1) == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W + 1);
+        if constexpr (Src::CONN == 8)
+            if ((top || left) && j > 0 && src.at(f, i - 1, j - 1) == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W - 1);
+        if (top && src.up(f, l, i, j)) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W);
+        if constexpr (Src::CONN == 8)
+            if ((top || right) && j + 1 < W && src.at(f, i - 1, j + 1) == l) uf_unite<__HIP_MEMORY_SCOPE_AGENT>(par, g, g - (uint32_t)W + 1);
     }
 }
 

@@ -195,11 +195,20 @@ class ImaginationEngine:
         if (proposer is None) != (tracker is None):
             raise ValueError("ImaginationEngine: proposer= and tracker= come together, " +
                              ("tracker=" if tracker is None else "proposer=") + " is missing")
-        # proposer: callable(uint8 [W,H,3], frame 0 turned upright) -> bool [M,W,H] mask proposals (SAM's mask generator alone);
+        # proposer: callable(uint8 [W,H,3], frame 0 turned upright) -> bool [M,W,H] mask proposals (SAM's mask generator alone), or
+        # "geometric": what stands above the support plane in frame 0's depth, on the GPU (segmentation.propose_masks, DESIGN.md
+        # section 2l; table-top scenes only);
         # tracker: callable(rgbs, labels0 uint8 [H,W]) -> uint8 [N,H,W] raw label images (XMem alone), or "geometric": the labels
         # are carried through the scan by depth and pose on the GPU (segmentation.track_labels)
         if isinstance(tracker, str) and tracker != "geometric":
             raise ValueError(f"ImaginationEngine: tracker= is a callable or \"geometric\", got {tracker!r}")
+        if isinstance(proposer, str):
+            if proposer != "geometric":
+                raise ValueError(f"ImaginationEngine: proposer= is a callable or \"geometric\", got {proposer!r}")
+            if cfg.scene_type not in (0, 3):
+                raise ValueError(f"ImaginationEngine: proposer=\"geometric\" takes what stands above one support plane for the objects, "
+                                 f"which holds for the table-top scenes (scene_type 0 and 3); scene_type {cfg.scene_type} (the shelf: "
+                                 f"several boards) has no single plane, pass a callable proposer")
         self.proposer, self.tracker = proposer, tracker
         if intrinsics is None:
             from .scene import INTRINSICS_REALSENSE_1280
@@ -249,7 +258,13 @@ class ImaginationEngine:
             rgbs_np = _np(rgbs)
             first = np.rot90(rgbs_np[0], 1)
             inside = np.rot90(_np(self.out_scene_bound_masks[0]) == 0)
-            labels0 = np.rot90(segmentation.proposals_to_labels(self.proposer(first), inside, ctx=self.ctx), 3)
+            if isinstance(self.proposer, str):             # "geometric": frame 0's depth in sensor orientation, the masks turned as the frame is
+                up = -np.asarray(physics_utils.GRAVITY_DIRECTION, np.float64)
+                proposals = np.rot90(segmentation.propose_masks(depths[0], loader.T_WC_data[0], intrinsics, cfg.scene_phys_bounds, up=up,
+                                                                ctx=self.ctx)[0], 1, axes=(1, 2))
+            else:
+                proposals = self.proposer(first)
+            labels0 = np.rot90(segmentation.proposals_to_labels(proposals, inside, ctx=self.ctx), 3)
             if isinstance(self.tracker, str):              # "geometric"
                 raw_masks = segmentation.track_labels(depths, loader.T_WC_data, intrinsics, np.ascontiguousarray(labels0),
                                                       cfg.scene_phys_bounds, ctx=self.ctx)

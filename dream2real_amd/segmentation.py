@@ -6,7 +6,9 @@ is DESIGN.md section 2d.
 Running SAM or XMem is out of scope: `proposals_to_labels` turns the mask generator's proposals into the first frame's label
 image (sam_seg.py:80-115 and integrate_masks); whatever produced the raw label images of all frames (XMem in
 the reference), `refine_masks` is the body of the `segment_associate` loop from there on and `load_cached_masks` its cache branch.
-`track_labels` is this package's own way from the first label image to all of them: by geometry, on the GPU."""
+`track_labels` is this package's own way from the first label image to all of them: by geometry, on the GPU,
+and `propose_masks` its own way to the proposals on a table-top scene: what stands above the support plane in the first frame's
+depth."""
 from __future__ import annotations
 
 import ctypes as C
@@ -148,6 +150,56 @@ def labeltrack_timing(ctx):
     """d2r_labeltrack_get_timing -> (upload, kernels, download) of the context's last track_labels, device-event milliseconds."""
     ms = np.zeros(3, np.float64)
     ctx.check(ctx.lib.d2r_labeltrack_get_timing(ctx.h, _lib.ptr(ms)))
+    return tuple(float(x) for x in ms)
+
+
+# the mirror of include/d2r.h's d2r_geoprop_params (tests/test_geoprop_host.py holds its layout to a C compiler's)
+class GeopropParams(C.Structure):
+    _fields_ = [("window_mm", C.c_uint32), ("h_min_mm", C.c_uint32), ("tau_mm", C.c_uint32), ("min_area", C.c_uint32), ("max_props", C.c_uint32)]
+
+
+GEOPROP_RECORD = np.dtype([(k, np.uint32) for k in ("root", "area", "i0", "j0", "i1", "j1")])
+GEOPROP_PLANE = np.dtype([(k, np.int32) for k in ("bin", "count", "inside", "above", "components")])
+
+
+def propose_masks(depth0, cam_pose, intrinsics, scene_bounds, *, ctx, up=(0.0, 0.0, 1.0), window_mm=5, h_min_mm=6, tau_mm=10,
+                  min_area=MIN_COMPONENT_AREA, max_props=255, return_labels=False):
+    """Mask proposals for a table-top scene from one depth frame, without a network (d2r_geoprop_masks): the
+    support plane is the fullest window of window_mm height bins along `up` among the pixels whose points lie in scene_bounds; what
+    stands h_min_mm or more above it, cut along depth steps of more than tau_mm millimetres into 4-connected pieces of at least
+    min_area pixels, is the proposals, the max_props largest at the most, numbered by their first pixel in raster order.  depth0
+    [H,W] metres (or uint16 millimetres) in sensor orientation, cam_pose [4,4] camera to world, intrinsics [3,3].
+    -> (bool [M,H,W], records [M] of root, area, i0, j0, i1, j1, plane record of bin, count, inside, above, components);
+    return_labels: also the uint16 [H,W] image of the proposals' numbers.  A frame without a pixel inside the bounds gives M = 0."""
+    d = depth_to_u16(depth0)
+    if d.ndim != 2:
+        raise ValueError(f"depth0 must be [H, W], got shape {d.shape}")
+    h, w = d.shape
+    T = np.ascontiguousarray(np.asarray(_np(cam_pose), np.float64).reshape(-1), np.float32)
+    if T.size != 16:
+        raise ValueError(f"cam_pose must be [4, 4], got {T.size} numbers")
+    K = np.asarray(_np(intrinsics), np.float64).reshape(3, 3)
+    K4 = np.ascontiguousarray([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float64)
+    b = _labeltrack_bounds(scene_bounds)
+    u = np.ascontiguousarray(np.asarray(_np(up), np.float64).reshape(-1))
+    if u.size != 3:
+        raise ValueError(f"up must be a vector of 3, got {u.size} numbers")
+    params = GeopropParams(int(window_mm), int(h_min_mm), int(tau_mm), int(min_area), int(max_props))
+    labels = np.zeros((h, w), np.uint16)
+    recs = np.zeros((max(int(max_props), 1), len(GEOPROP_RECORD.names)), np.uint32)
+    m, plane = C.c_uint32(0), np.zeros(len(GEOPROP_PLANE.names), np.int32)
+    ctx.check(ctx.lib.d2r_geoprop_masks(ctx.h, _lib.ptr(b), _lib.ptr(u), C.byref(params), w, h, _lib.ptr(K4), _lib.ptr(d), _lib.ptr(T),
+                                        _lib.ptr(labels), _lib.ptr(recs), C.byref(m), _lib.ptr(plane)))
+    masks = labels[None] == np.arange(1, m.value + 1, dtype=np.uint16)[:, None, None]
+    out = (masks, np.ascontiguousarray(recs[:m.value]).view(GEOPROP_RECORD).reshape(-1), plane.view(GEOPROP_PLANE)[0])
+    return out + (labels,) if return_labels else out
+
+
+def geoprop_timing(ctx):
+    """d2r_geoprop_get_timing -> (upload, heights and histogram, components, selection and label image, download) of the context's
+    last propose_masks, device-event milliseconds."""
+    ms = np.zeros(5, np.float64)
+    ctx.check(ctx.lib.d2r_geoprop_get_timing(ctx.h, _lib.ptr(ms)))
     return tuple(float(x) for x in ms)
 
 

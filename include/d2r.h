@@ -1056,6 +1056,46 @@ D2R_API int d2r_labeltrack_scan(d2r_ctx *ctx, const double *bounds, const d2r_la
 /* Device-event times of the context's last d2r_labeltrack_scan: ms_out host [3] = upload, kernels, download, in milliseconds. */
 D2R_API int d2r_labeltrack_get_timing(d2r_ctx *ctx, double *ms_out);
 
+/* ------------------------------------------------- mask proposals from depth and the support plane (proposer="geometric")
+ *
+ * This package's own stand-in for the segmentation network (SAM's mask generator) the reference takes its mask proposals from, for
+ * table-top scenes; nothing here stands where reference code stands.  A pixel of frame 0 with depth is back-projected in fp64
+ * (section 2d) and is `inside` when its point lies in the bounds; its height is floor(1000 (up . p) + 0.5) millimetres.  The support
+ * plane b* is the centre of the fullest window of window_mm height bins (ties to the lowest); a pixel is `above` when it is inside
+ * at b* + h_min_mm or higher; two 4-neighbours are linked when both are above and their depths differ by tau_mm millimetres at the
+ * most; the connected sets of at least min_area pixels, the max_props largest of them (area ties to the smaller first pixel),
+ * numbered 1 .. M by their first pixel in raster order, are the proposals.  Integer atomics only: the result does not depend on
+ * the order the threads ran in.
+ */
+#define D2R_GEOPROP_REC_WORDS 6u       /* root (raster index of the first pixel), area, i0, j0, i1, j1 (rows, columns, inclusive) */
+#define D2R_GEOPROP_PLANE_WORDS 5u     /* b*, pixels in its window, inside pixels, above pixels, components before the selection */
+#define D2R_GEOPROP_MAX_BINS (1u << 16)
+
+typedef struct d2r_geoprop_params {
+    uint32_t window_mm;       /* odd, 1 .. 65535: the height bins summed around a candidate plane; 5 by default in the Python layer */
+    uint32_t h_min_mm;        /* 0 .. 65535: a pixel is above from b* + h_min_mm on; 6 */
+    uint32_t tau_mm;          /* 0 .. 65535: the largest depth step between two linked neighbours, millimetres; 10 */
+    uint32_t min_area;        /* pixels: smaller components are dropped; 200 */
+    uint32_t max_props;       /* 1 .. D2R_PROP_MAX: the most proposals returned */
+} d2r_geoprop_params;
+
+/* bounds host [6]: xmin ymin zmin xmax ymax zmax; up host [3]: a unit vector (to 1e-6), the direction heights are measured along;
+ * d16 host [h][w] millimetres; cam_pose host [16] fp32 row-major camera-to-world (OpenCV); K host [4]: fx fy cx cy.  labels_out host
+ * [h][w]: 0 or the proposal's number; recs_out host [max_props][D2R_GEOPROP_REC_WORDS]: rows 0 .. M - 1 filled, the others zero;
+ * *n_out = M; plane_out host [D2R_GEOPROP_PLANE_WORDS].  Without an inside pixel there is no plane: everything comes back zero, which
+ * is a result, not a failure.  Refused with D2R_ERR_INVALID before any device work, outputs untouched: null arguments, w h = 0 or
+ * above D2R_LABELTRACK_MAX_PIXELS, a non-rigid or non-finite pose, a focal length that is not finite and > 0, a non-finite principal
+ * point, bounds that are not finite with min < max or span more than D2R_GEOPROP_MAX_BINS height bins, an up that is not of unit
+ * length, a parameter outside its range.  Synchronous. */
+D2R_API int d2r_geoprop_masks(d2r_ctx *ctx, const double *bounds, const double *up, const d2r_geoprop_params *params, uint32_t w, uint32_t h,
+                              const double *K, const uint16_t *d16, const float *cam_pose, uint16_t *labels_out, uint32_t *recs_out,
+                              uint32_t *n_out, int32_t *plane_out);
+
+/* Device-event times of the context's last d2r_geoprop_masks: ms_out host [5] = upload; heights and histogram; plane choice, links,
+ * labelling, statistics and the candidate list; selection, numbering and the label image; download, in milliseconds.  The second
+ * and the third interval each hold one small copy to the host and the host's part of the rule. */
+D2R_API int d2r_geoprop_get_timing(d2r_ctx *ctx, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif
