@@ -117,6 +117,11 @@ PROTOTYPES = {
     "d2r_labeltrack_get_timing": (_int, (_ptr, _ptr)),
     "d2r_geoprop_masks": (_int, (_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr)),
     "d2r_geoprop_get_timing": (_int, (_ptr, _ptr)),
+    "d2r_caption_embed": (_int, (_ptr, _ptr, _ptr, _ptr, _ptr)),
+    "d2r_caption_vote": (_int, (_ptr, _ptr, _ptr, _u32, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr)),
+    "d2r_caption_names": (_int, (_ptr, _ptr, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr)),
+    "d2r_caption_load_packed": (_int, (_ptr, _ptr, _u64, _ptr, _u32, _u32)),
+    "d2r_caption_get_timing": (_int, (_ptr, _ptr)),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -536,6 +541,70 @@ def thumbs_timing(ctx):
     """d2r_thumbs_get_timing -> (upload, kernels, download) of the context's last thumbs_plan plus thumbs_fill, device-event milliseconds."""
     ms = np.zeros(3, np.float64)
     check(load().d2r_thumbs_get_timing(_h(ctx), ptr(ms)), _h(ctx))
+    return tuple(float(x) for x in ms)
+
+
+CAPTION_MAX_K, CAPTION_MAX_V, CAPTION_MAX_D = 8, 8192, 1024     # D2R_CAPTION_MAX_K / _V / _D
+
+
+def caption_embed(ctx, scorer, n_thumbs: int, crops: bool = False, pixel_values: bool = False):
+    """d2r_caption_embed: the context's n_thumbs packed thumbnails (thumbs_fill, or caption_load_packed) ->
+    L2-normalised embeddings float32 [n_thumbs, proj]; with crops / pixel_values also uint8 [n_thumbs,S,S,3] / float32
+    [n_thumbs,3,S,S] (a tuple in that order).  scorer: an engine.ClipScorer."""
+    S, D = scorer.cfg["image_size"], scorer.cfg["proj"]
+    emb = np.zeros((max(n_thumbs, 1), D), np.float32)
+    u8 = np.zeros((max(n_thumbs, 1), S, S, 3), np.uint8) if crops else None
+    pv = np.zeros((max(n_thumbs, 1), 3, S, S), np.float32) if pixel_values else None
+    check(load().d2r_caption_embed(_h(ctx), scorer.h, ptr(emb), ptr(u8), ptr(pv)), _h(ctx))
+    out = (emb[:n_thumbs],) + ((u8[:n_thumbs],) if crops else ()) + ((pv[:n_thumbs],) if pixel_values else ())
+    return out if len(out) > 1 else out[0]
+
+
+def caption_vote(ctx, embeds, obj_of, class_embeds, n_objs: int, k: int):
+    """d2r_caption_vote (parity hook): embeds float32 [T,D], obj_of [T] (0 .. n_objs - 1, non-decreasing), class_embeds float32 [V,D]
+    -> (indices uint32 [n_objs,k], scores float32 [n_objs,k])."""
+    c = np.ascontiguousarray(class_embeds, np.float32)
+    e = np.ascontiguousarray(embeds, np.float32).reshape(-1, c.shape[1])
+    o = np.ascontiguousarray(obj_of, np.uint32).reshape(-1)
+    if o.shape[0] != e.shape[0]:
+        raise ValueError(f"{o.shape[0]} objects for {e.shape[0]} embeddings")
+    idx, sc = np.zeros((n_objs, k), np.uint32), np.zeros((n_objs, k), np.float32)
+    check(load().d2r_caption_vote(_h(ctx), ptr(e), ptr(o), e.shape[0], ptr(c), c.shape[0], c.shape[1], n_objs, k, ptr(idx), ptr(sc)), _h(ctx))
+    return idx, sc
+
+
+def caption_names(ctx, scorer, class_embeds, n_objs: int, k: int):
+    """d2r_caption_names: the context's thumbnails of the plan's objects 1 .. n_objs -> (indices uint32 [n_objs,k] into class_embeds
+    float32 [V,D], scores float32 [n_objs,k]); only these cross back to the host.  n_objs must be the plan's num_objs - 1."""
+    c = np.ascontiguousarray(class_embeds, np.float32)
+    idx, sc = np.zeros((n_objs, k), np.uint32), np.zeros((n_objs, k), np.float32)
+    check(load().d2r_caption_names(_h(ctx), scorer.h, ptr(c), c.shape[0], c.shape[1], n_objs, k, ptr(idx), ptr(sc)), _h(ctx))
+    return idx, sc
+
+
+def caption_load_packed(ctx, images, obj_of, n_objs: int):
+    """d2r_caption_load_packed (parity hook): uint8 [h,w,3] images of any sizes, packed at offsets that are multiples of 4 as
+    thumbs_fill packs them, stand on the context where a plan's thumbnails would.  obj_of: the object 0 .. n_objs - 1 per image,
+    non-decreasing.  -> the packed buffer."""
+    recs, parts, off = [], [], 0
+    for img, o in zip(images, obj_of):
+        a = np.ascontiguousarray(img, np.uint8)
+        assert a.ndim == 3 and a.shape[2] == 3
+        recs.append([int(o), a.shape[0], a.shape[1], off & 0xffffffff, off >> 32])
+        pad = -a.size % 4
+        parts += [a.reshape(-1), np.zeros(pad, np.uint8)]
+        off += a.size + pad
+    packed = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
+    r = np.ascontiguousarray(recs, np.uint32).reshape(-1, 5)
+    check(load().d2r_caption_load_packed(_h(ctx), ptr(packed), packed.size, ptr(r), r.shape[0], n_objs), _h(ctx))
+    return packed
+
+
+def caption_timing(ctx):
+    """d2r_caption_get_timing -> (upload, preprocess, tower, scoring, download) of the context's last caption call, device-event
+    milliseconds."""
+    ms = np.zeros(5, np.float64)
+    check(load().d2r_caption_get_timing(_h(ctx), ptr(ms)), _h(ctx))
     return tuple(float(x) for x in ms)
 
 

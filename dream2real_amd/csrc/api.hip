@@ -306,7 +306,7 @@ void d2r_ctx_destroy(d2r_ctx *c)
                             &c->tv_mats, &c->tv_bg_frame, &c->tv_bg_depth, &c->tv_depth, &c->ct_in, &c->ct_ws, &c->lt_in, &c->lt_ws, &c->gp_in, &c->gp_ws,
                             &c->mv_in, &c->mv_recs, &c->mv_queue, &c->mv_shade, &c->mv_keys, &c->mv_out,
                             &c->mask_in, &c->mask_out, &c->mask_ws, &c->thumb_in, &c->thumb_ws, &c->thumb_out,
-                            &c->prop_in, &c->prop_ws, &c->prop_out};
+                            &c->prop_in, &c->prop_ws, &c->prop_out, &c->cap_tab, &c->cap_emb, &c->cap_ws, &c->cap_cls};
     for (auto *b : bufs)
         if (b->p) hipFree(b->p);
     for (auto &b : c->clipws)

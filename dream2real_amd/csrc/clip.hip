@@ -2857,15 +2857,19 @@ static double bicubic_filter(double x)
 
 // Pillow's antialiased bicubic coefficient tables (Resample.c precompute_coeffs +
 // normalize_coeffs_8bpc), restated; oracle counterpart: d2r_oracle_resample_coeffs
-static int resample_coeffs(int in_size, int out_size, std::vector<int> &bounds, std::vector<int> &kk)
+// (`first`, `count`: only the output positions first .. first + count - 1, entry i of the tables being position first + i; captions.hip
+// builds the columns a centre crop reads out of a side of up to 2^20)
+static int resample_coeffs(int in_size, int out_size, std::vector<int> &bounds, std::vector<int> &kk, int first = 0, int count = -1)
 {
     double scale = (double)in_size / out_size, filterscale = scale < 1.0 ? 1.0 : scale;
     double support = 2.0 * filterscale;
     int ksize = (int)ceil(support) * 2 + 1;
-    bounds.assign((size_t)out_size * 2, 0);
-    kk.assign((size_t)out_size * ksize, 0);
+    if (count < 0) count = out_size - first;
+    bounds.assign((size_t)count * 2, 0);
+    kk.assign((size_t)count * ksize, 0);
     std::vector<double> k(ksize);
-    for (int xx = 0; xx < out_size; xx++) {
+    for (int i = 0; i < count; i++) {
+        const int xx = first + i;
         double center = (xx + 0.5) * scale, ww = 0.0, ss = 1.0 / filterscale;
         int xmin = (int)(center - support + 0.5);
         if (xmin < 0) xmin = 0;
@@ -2878,11 +2882,11 @@ static int resample_coeffs(int in_size, int out_size, std::vector<int> &bounds, 
         }
         for (int x = 0; x < ksize; x++) {
             double v = x < xmax ? (ww != 0.0 ? k[x] / ww : k[x]) : 0.0;
-            kk[(size_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS))
-                                               : (int)(0.5 + v * (1 << PRECISION_BITS));
+            kk[(size_t)i * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS))
+                                              : (int)(0.5 + v * (1 << PRECISION_BITS));
         }
-        bounds[xx * 2] = xmin;
-        bounds[xx * 2 + 1] = xmax;
+        bounds[i * 2] = xmin;
+        bounds[i * 2 + 1] = xmax;
     }
     return ksize;
 }
@@ -3732,6 +3736,13 @@ extern "C" int d2r_text_encode(d2r_ctx *ctx, const d2r_text *tt, const int32_t *
 
 uint32_t d2r_clip_image_size(const d2r_clip *c) { return c->desc.image_size; }
 uint32_t d2r_clip_proj_dim(const d2r_clip *c) { return c->desc.proj_dim; }
+// what captions.hip needs of the tower's input layout and of the table builder (d2r_internal.h)
+uint32_t d2r_clip_patch_size(const d2r_clip *c) { return c->desc.patch_size; }
+uint32_t d2r_clip_patch_stride(const d2r_clip *c) { return c->Kp_pad; }
+int d2r_clip_resample_coeffs(int in_size, int out_size, int first, int count, std::vector<int> &bounds, std::vector<int> &kk)
+{
+    return resample_coeffs(in_size, out_size, bounds, kk, first, count);
+}
 
 // ------------------------------------------------------------ parity hook: one fp8 product ("fp8 blocks")
 //

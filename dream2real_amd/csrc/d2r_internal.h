@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -106,6 +108,23 @@ struct D2rThumbPlan {
     std::vector<uint32_t> recs;                  // [n_recs][D2R_THUMB_REC_WORDS]
 };
 
+// captions.hip: the packed thumbnails d2r_thumbs_fill (or the parity hook d2r_caption_load_packed) left in thumb_out, as
+// d2r_caption_embed / d2r_caption_names read them.  A new plan, or anything else that writes thumb_out, clears `filled`.
+struct D2rCaptionSrc {
+    bool filled = false;
+    uint32_t n_objs = 0;                         // objects 1 .. n_objs of the plan
+    uint64_t total = 0;                          // bytes of the packed buffer
+    std::vector<uint32_t> recs;                  // [T][5] in record order: object - 1, rows, cols, offset low, offset high
+};
+
+// ... the resize geometry and the coefficient tables of one (rows, cols, S, P), cut to the S positions the centre crop reads; a side
+// that is S already has no tables.  Built on first use and kept by the context.
+struct D2rCaptionTables {
+    int ks_h = 0, ks_v = 0, need_h = 0, need_v = 0, left = 0, top = 0;
+    int band_rows = 0;                           // the largest vertical support of a band of P output rows
+    std::vector<int> bh, kh, bv, kv;             // bounds_h [S][2], kk_h [S][ks_h], bounds_v [S][2], kk_v [S][ks_v]
+};
+
 // Layer-0 reuse of background tokens inside d2r_render_score (clip.hip "layer-0 reuse"): the frame rectangles the candidates
 // of the chunk touched, and the background's own pre-LayerNorm residual rows and layer-0 q / k / v rows (d2r_clip_layer0_background)
 struct ClipL0Reuse {
@@ -156,6 +175,14 @@ struct d2r_ctx {
     Buf thumb_in, thumb_ws, thumb_out;   // masks.hip, object thumbnails: frames + noise + records (one D2rStage), statistics / labelling / blur workspace, the packed thumbnails
     D2rThumbPlan thumb_plan;     // ... the records of the last d2r_thumbs_plan
     D2rStageTimer thumb_timer[2];   // ... upload / kernels / download of the last plan and of the last fill (d2r_thumbs_get_timing adds them)
+    D2rCaptionSrc cap_src;       // captions.hip: what thumb_out holds for the captioner
+    Buf cap_tab, cap_emb, cap_ws, cap_cls;   // ... record descriptors + coefficient tables (one D2rStage), the thumbnails' embeddings, parity outputs / vote inputs and results (one D2rStage), the class embeddings
+    uint64_t cap_cls_key[3] = {0, 0, 0};     // ... V, D and the FNV-1a hash of the class embeddings cap_cls holds
+    bool cap_cls_valid = false;
+    std::map<std::array<uint32_t, 4>, D2rCaptionTables> cap_sizes;   // ... tables per (rows, cols, S, P), host side
+    D2rStageTimer cap_ev[4];     // ... a pass of preprocess + tower, the scoring, a pass's downloads, the class embeddings' upload
+    double cap_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // ... upload, preprocess, tower, scoring, download of the last caption call (d2r_caption_get_timing)
+    bool cap_timed = false;
     Buf prop_in, prop_ws, prop_out;   // proposals.hip: the uploaded proposals + scene mask, the packed planes / union-find parents / records / pair matrix (one D2rStage), the label image
     D2rStageTimer prop_timer;    // ... upload / kernels / download of the last d2r_proposals_labels (d2r_proposals_get_timing)
     D2rStageTimer mask_timer;    // ... upload / kernels / download of the last batch call (d2r_masks_get_timing)
@@ -269,6 +296,12 @@ int d2r_pcd_check_view(d2r_ctx *ctx, const d2r_pcd_view *view);      // pcd.hip:
 // phys.hip: the host side the two physics pre-filters (hulls + GJK in phys.hip, points against the TSDF field in sdfphys.hip) share
 int d2r_phys_orientations(d2r_ctx *, const d2r_phys_params *, uint32_t N, uint64_t *oris_out);      // checks N against sample_res -> orientations per position
 std::vector<uint8_t> d2r_phys_orientation_mask(const d2r_phys_params *, const float *pose_batch, const uint8_t *valid_io, uint32_t oris);   // [oris] 0: duplicate orientation / not regraspable
+
+// clip.hip: what captions.hip reaches of the vision tower (the tower entry itself, d2r_clip_forward, is declared where it is called)
+struct d2r_clip;
+uint32_t d2r_clip_patch_size(const d2r_clip *);
+uint32_t d2r_clip_patch_stride(const d2r_clip *);      // bf16 elements per patch row of the tower's input (Kp_pad)
+int d2r_clip_resample_coeffs(int in_size, int out_size, int first, int count, std::vector<int> &bounds, std::vector<int> &kk);   // Pillow's fixed-point bicubic tables as prep_tables builds them, for the output positions first .. first + count - 1 -> ksize
 
 // api.hip: what the entry points that score frames share
 struct d2r_clip;

@@ -816,6 +816,7 @@ int d2r_thumbs_plan(d2r_ctx *ctx, const uint8_t *rgbs, const uint8_t *masks_u8, 
     if (recs_out && *n_recs < count) return d2r_fail(ctx, D2R_ERR_INVALID, "thumbnails: recs_out holds fewer records than the plan has");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
     ctx->thumb_plan.valid = false;
+    ctx->cap_src.filled = false;
     const size_t px = (size_t)w * h, tot = px * n;
     const bool test0 = f_first == 0 && nobj > 0;            // the container test runs on frame 0 alone
     // objects per pass of the container test: a pixel costs masks_label's 44 bytes and one more for the complement image
@@ -955,6 +956,7 @@ int d2r_thumbs_fill(d2r_ctx *ctx, const uint8_t *noise_u8, uint8_t *out_u8, uint
                  o_b0 = ws.add((size_t)slots * flat_words * 8), o_rowv = ws.add((size_t)slots * px * 2), o_blur = ws.add(bit_words * 8),
                  o_dil = ws.add(bit_words * 8);
     int rc;
+    ctx->cap_src.filled = false;
     if ((rc = ws.reserve()) || (rc = d2r_reserve(ctx, ctx->thumb_out, (size_t)P.total))) return rc;
     D2rStageTimer &timer = ctx->thumb_timer[1];
     if ((rc = timer.mark(ctx, 0)) || (rc = ws.upload(o_noise, noise_u8, px * 3))) return rc;
@@ -979,6 +981,16 @@ int d2r_thumbs_fill(d2r_ctx *ctx, const uint8_t *noise_u8, uint8_t *out_u8, uint
     if ((rc = timer.mark(ctx, 3))) return rc;
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));         // the host vectors above were read by then
     timer.done();
+    // the packed thumbnails stay in thumb_out until the next plan: captions.hip reads them there
+    D2rCaptionSrc &C = ctx->cap_src;
+    C.recs.clear();
+    for (const ThumbRec &r : recs) {
+        const uint32_t five[5] = {r.obj - 1, r.rows, r.cols, (uint32_t)r.off, (uint32_t)(r.off >> 32)};
+        C.recs.insert(C.recs.end(), five, five + 5);
+    }
+    C.n_objs = P.recs.empty() ? 0u : P.recs[P.recs.size() - D2R_THUMB_REC_WORDS];      // objects outermost: the last record's
+    C.total = P.total;
+    C.filled = true;
     return D2R_OK;
 }
 
@@ -992,6 +1004,7 @@ int d2r_thumbs_blur_bits(d2r_ctx *ctx, const uint8_t *bits_u8, uint32_t w, uint3
     D2R_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t ww = (w + 63) / 64;
     const size_t px = (size_t)w * h, words = (size_t)h * ww;
+    ctx->cap_src.filled = false;                             // thumb_out is about to hold this image
     D2rStage ws(ctx, ctx->thumb_ws);
     const size_t o_img = ws.add(px), o_b0 = ws.add(words * 8), o_rowv = ws.add(px * 2), o_blur = ws.add(words * 8), o_dil = ws.add(words * 8);
     if ((rc = ws.reserve()) || (rc = d2r_reserve(ctx, ctx->thumb_out, px)) || (rc = ws.upload(o_img, bits_u8, px))) return rc;

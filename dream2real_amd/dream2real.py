@@ -191,7 +191,18 @@ class ImaginationEngine:
         self.depths_gt = depths_gt                       # [L, h, w] sensor depth of the render views (dream2real.py:117-118), or None
         self.data_dir = cfg.data_dir
         self.lang_model, self.segmentor = lang_model, segmentor
-        self.captioner = captioner                       # callable(list of uint8 [h,w,3] thumbnails) -> list of captions, or None
+        # captioner: callable(list of uint8 [h,w,3] thumbnails) -> list of captions, or None, or "clip": a caption.ClipCaptioner built
+        # from the engine's own scorer, text encoder and tokenizer names the objects from a closed vocabulary
+        if isinstance(captioner, str):
+            if captioner != "clip":
+                raise ValueError(f"ImaginationEngine: captioner= is a callable or \"clip\", got {captioner!r}")
+            missing = [n for n, v in (("scorer", scorer), ("text_encoder=", text_encoder), ("tokenizer=", tokenizer)) if v is None]
+            if missing:
+                raise ValueError("ImaginationEngine: captioner=\"clip\" names the objects with the CLIP towers, " + " and ".join(missing) +
+                                 (" is" if len(missing) == 1 else " are") + " missing")
+            from . import caption
+            captioner = caption.ClipCaptioner(ctx, scorer, text_encoder, tokenizer)
+        self.captioner = captioner
         if (proposer is None) != (tracker is None):
             raise ValueError("ImaginationEngine: proposer= and tracker= come together, " +
                              ("tracker=" if tracker is None else "proposer=") + " is missing")

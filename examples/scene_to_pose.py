@@ -1,5 +1,5 @@
 """A scan folder and a settings file in, the best pose out: the three calls of ImaginationEngine.
-    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--vis-backend tsdf] [--refine-poses] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy | --proposals FILE.npy --geometric-tracker | --geometric-proposer]
+    python examples/scene_to_pose.py configs/shopping/pcd.json data/shopping "put the apple in the bowl" clip_dir [--vis] [--vis-backend tsdf] [--refine-poses] [--dump-thumbnails DIR] [--proposals FILE.npy --tracked FILE.npy | --proposals FILE.npy --geometric-tracker | --geometric-proposer] [--clip-captioner]
 --vis also writes best_pose_vis.png (and, without use_vis_pcds, cost_volume.png) into the folder.
 --vis-backend tsdf renders the candidates from colour-TSDF volumes fused from the scan instead of the settings
 file's visual model (NeRF snapshots, or point clouds with use_vis_pcds, which it switches off).
@@ -13,6 +13,9 @@ between them instead of reading XMem_masks/.
 section 2k), no tracking network and no recording of one.
 --geometric-proposer: no segmentation model and no recording at all, for a table-top scene (scene_type 0 or 3): the proposals are
 what stands above the support plane in the first frame's depth and the geometric tracker carries them.
+--clip-captioner: no captioning model and no captions.json: the objects are named from the package's vocabulary of object names by the
+CLIP checkpoint's own towers, the thumbnails never leaving the GPU; captions.json and caption_scores.json are
+written.  With --geometric-proposer only lang_cache.json is still read.
 The folder holds poses.txt, images/, depth/, XMem_masks/ (use_cache_segs), captions.json and lang_cache.json (a
 CachedLangModel file); clip_dir holds a CLIP checkpoint: model.safetensors, vocab.json, merges.txt."""
 import os
@@ -57,6 +60,11 @@ if geometric_proposer:
     argv.remove("--geometric-proposer")
     if recorded or geometric:
         sys.exit("--geometric-proposer stands alone: it implies the geometric tracker and takes no recorded proposals")
+if "--clip-captioner" in argv:
+    argv.remove("--clip-captioner")
+    models_captioner = dict(captioner="clip")
+else:
+    models_captioner = {}
 vis = "--vis" in argv
 config_file, data_dir, user_instr, clip_dir = [a for a in argv if a != "--vis"][:4]
 cfg = PathConfig.from_json(config_file, data_dir, use_cache_segs=not (recorded or geometric_proposer), phys_backend="tsdf", **backend)
@@ -67,6 +75,7 @@ if recorded:
                   tracker="geometric" if geometric else lambda frames, labels0: np.load(recorded["--tracked"]))
 if geometric_proposer:
     models = dict(proposer="geometric", tracker="geometric")
+models.update(models_captioner)
 ctx = engine.Context(0)
 clip_cfg, state = load_clip_safetensors(os.path.join(clip_dir, "model.safetensors"))
 imagination = ImaginationEngine(cfg, ctx, engine.ClipScorer(ctx, clip_cfg, state),

@@ -1096,6 +1096,54 @@ D2R_API int d2r_geoprop_masks(d2r_ctx *ctx, const double *bounds, const double *
  * and the third interval each hold one small copy to the host and the host's part of the rule. */
 D2R_API int d2r_geoprop_get_timing(d2r_ctx *ctx, double *ms_out);
 
+/* ------------------------------------------------- object names from the package's own CLIP towers (captioner="clip")
+ *
+ * This package's own stand-in for the captioning network (BLIP-2) and the language model's merging of the per-view captions
+ * (reference caption.py:132-160); nothing here stands where reference code stands.  The thumbnails d2r_thumbs_fill left packed on
+ * the device (they stay there until the context's next d2r_thumbs_plan) go through HF's CLIPImageProcessor (shortest side to S with
+ * Pillow's antialiased bicubic, centre crop) in one launch whatever their sizes, through the vision tower, and are compared with the
+ * embeddings of a closed vocabulary of names: cos[t][v] in fp32 by 64 partial sums joined by the xor butterfly, summed per object
+ * over its thumbnails in record order; the k best classes per object by (score descending, index ascending) are the answer.
+ */
+#define D2R_CAPTION_MAX_K 8u
+#define D2R_CAPTION_MAX_V 8192u       /* classes per call */
+#define D2R_CAPTION_MAX_D 1024u       /* embedding width: a multiple of 64 */
+
+/* Needs a d2r_thumbs_plan and a d2r_thumbs_fill on this context (or d2r_caption_load_packed).  embeds_out host [T][proj_dim], T the
+ * accepted records of the plan in record order, L2-normalised; crops_u8_out (optional) host [T][S][S][3] the resized and cropped
+ * images; pixel_values_out (optional) host [T][3][S][S] what the tower's patches were rounded from.  Refused with D2R_ERR_INVALID
+ * before any device work, outputs untouched: null arguments, no filled plan on this context; D2R_ERR_UNSUPPORTED: a thumbnail whose
+ * resized long side would pass 2^20 pixels or whose band does not fit in LDS. */
+D2R_API int d2r_caption_embed(d2r_ctx *ctx, const d2r_clip *clip, float *embeds_out, uint8_t *crops_u8_out, float *pixel_values_out);
+
+/* Parity hook, the scoring launch alone on host arrays: embeds host [T][D], obj_of host [T] the object 0 .. n_objs - 1 of every
+ * thumbnail, non-decreasing; class_embeds host [V][D].  idx_out host [n_objs][k], score_out host [n_objs][k]; an object without a
+ * thumbnail scores 0 for every class, and a score that is no number (a NaN embedding) ranks, and is reported, as minus infinity.  The
+ * class embeddings are uploaded once per (V, D, contents).  Refused with D2R_ERR_INVALID
+ * before any device work, outputs untouched: null arguments, V = 0 or above D2R_CAPTION_MAX_V, D no multiple of 64 or above
+ * D2R_CAPTION_MAX_D, k outside 1 .. min(D2R_CAPTION_MAX_K, V), n_objs outside 1 .. 255, a class embedding that is not finite, an
+ * obj_of that decreases or reaches n_objs. */
+D2R_API int d2r_caption_vote(d2r_ctx *ctx, const float *embeds, const uint32_t *obj_of, uint32_t T, const float *class_embeds, uint32_t V,
+                             uint32_t D, uint32_t n_objs, uint32_t k, uint32_t *idx_out, float *score_out);
+
+/* The fused call: the context's thumbnails -> idx_out host [n_objs][k], score_out host [n_objs][k] for the objects 1 .. n_objs =
+ * num_objs - 1 of the plan; nothing else crosses to the host.  Refused like the two calls above, when D is not the clip's proj_dim,
+ * and when n_objs is not the number of objects the context's thumbnails are of (the outputs would not fit). */
+D2R_API int d2r_caption_names(d2r_ctx *ctx, const d2r_clip *clip, const float *class_embeds, uint32_t V, uint32_t D, uint32_t n_objs,
+                              uint32_t k, uint32_t *idx_out, float *score_out);
+
+/* Parity hook: a packed buffer of thumbnails from the host in place of a plan and a fill, so that a test chooses the sizes.  recs
+ * host [n_recs][5]: object 0 .. n_objs - 1 (non-decreasing), rows, cols, offset low, offset high; an image is rows x cols x 3 bytes
+ * at its offset, a multiple of 4.  Refused with D2R_ERR_INVALID: null arguments, no record or object, a record outside the buffer,
+ * rows or cols outside 1 .. 16384. */
+D2R_API int d2r_caption_load_packed(d2r_ctx *ctx, const uint8_t *packed_u8, uint64_t total_bytes, const uint32_t *recs, uint32_t n_recs,
+                                    uint32_t n_objs);
+
+/* Device-event times of the context's last d2r_caption_embed / d2r_caption_vote / d2r_caption_names: ms_out host [5] = upload,
+ * preprocess, tower, scoring, download, in milliseconds (a stage the call did not run is 0; the upload includes the class
+ * embeddings when the call brought new ones). */
+D2R_API int d2r_caption_get_timing(d2r_ctx *ctx, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif
