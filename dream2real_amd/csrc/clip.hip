@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <deque>
+#include <memory>
 #include <mutex>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -70,21 +71,37 @@ struct PrepCache {
     uint32_t w, h;
     int rot90;
     ResampleTables R;
+    D2rDev<int> tables;              // what R's four pointers point into
+};
+
+// A tower handle's device memory: one hipMalloc per take(), owned from the moment it succeeds, freed with the handle.
+struct DevPool {
+    std::vector<D2rDev<uint8_t>> bufs;
+    // `count` elements of T, or nullptr with the context's error set (D2R_ERR_MEMORY)
+    template <class T>
+    T *take(d2r_ctx *ctx, size_t count, const char *what)
+    {
+        D2rDev<uint8_t> b;
+        if (b.alloc(ctx, count * sizeof(T), what)) return nullptr;
+        bufs.push_back(std::move(b));
+        return (T *)bufs.back().get();
+    }
 };
 
 struct d2r_clip {
     d2r_ctx *ctx;
     d2r_clip_desc desc;
     uint32_t T, Kp, Kp_pad;
-    std::vector<void *> allocs;
+    mutable DevPool mem;             // the weights (create) and the fp8 copies (under f8_mu)
     ClipWeights w;
     std::vector<ClipWeights::Layer> layers;
-    std::deque<PrepCache> prep;      // resampling tables per (w, h, rot90), built on first use (deque: stable references)
-    std::mutex prep_mu;              // two threads may score different frame sizes with one model
+    // caches a forward call fills through a const handle
+    mutable std::deque<PrepCache> prep;      // resampling tables per (w, h, rot90), built on first use (deque: stable references)
+    mutable std::mutex prep_mu;              // two threads may score different frame sizes with one model
     // "fp8 blocks": e4m3 copies of the four Linear weights of every layer + their per-matrix scales, built on first use
     struct F8Layer { const uint8_t *w_qkv, *w_o, *w_fc1, *w_fc2; float s_qkv, s_o, s_fc1, s_fc2; };
-    std::vector<F8Layer> f8;
-    std::mutex f8_mu;
+    mutable std::vector<F8Layer> f8;
+    mutable std::mutex f8_mu;
 };
 
 __device__ __forceinline__ uint16_t f2bf(float x)
@@ -2892,7 +2909,7 @@ static int resample_coeffs(int in_size, int out_size, std::vector<int> &bounds, 
 }
 
 // Resampling geometry + Pillow coefficient tables for one frame size, uploaded once.
-static int prep_tables(d2r_ctx *ctx, d2r_clip *clip, uint32_t w, uint32_t h, int rot90, const PrepCache **out)
+static int prep_tables(d2r_ctx *ctx, const d2r_clip *clip, uint32_t w, uint32_t h, int rot90, const PrepCache **out)
 {
     std::lock_guard<std::mutex> lock(clip->prep_mu);
     for (const PrepCache &pc : clip->prep)
@@ -2933,15 +2950,16 @@ static int prep_tables(d2r_ctx *ctx, d2r_clip *clip, uint32_t w, uint32_t h, int
     all.insert(all.end(), kh.begin(), kh.end());
     all.insert(all.end(), bv.begin(), bv.end());
     all.insert(all.end(), kv.begin(), kv.end());
-    int *dev = nullptr;
-    if (hipMalloc(&dev, all.size() * sizeof(int)) != hipSuccess) return d2r_fail(ctx, D2R_ERR_MEMORY, "hipMalloc failed");
-    clip->allocs.push_back(dev);
+    D2rDev<int> tables;
+    int rc;
+    if ((rc = tables.alloc(ctx, all.size() * sizeof(int), "the resampling tables"))) return rc;
+    int *dev = tables.get();
     D2R_HIP(ctx, hipMemcpy(dev, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
     R.bounds_h = dev + o_bh;
     R.kk_h = dev + o_kh;
     R.bounds_v = dev + o_bv;
     R.kk_v = dev + o_kv;
-    clip->prep.push_back(PrepCache{w, h, rot90, R});
+    clip->prep.push_back(PrepCache{w, h, rot90, R, std::move(tables)});
     *out = &clip->prep.back();
     return D2R_OK;
 }
@@ -3061,29 +3079,27 @@ static int launch_gemm_f8(d2r_ctx *ctx, const uint8_t *A8, const uint8_t *a_scal
 }
 
 // vision tower: streamed attention, one workgroup per (image, head, group of eight query tiles)
-static void launch_attention_vision(d2r_ctx *ctx, const uint16_t *QKV, uint16_t *AO, uint32_t T, uint32_t d, uint32_t M_pad,
-                                    uint32_t n_heads, uint32_t n, uint8_t *q8_scales = nullptr)
+template <bool Q8>
+static void launch_attention_s(d2r_ctx *ctx, const uint16_t *QKV, uint16_t *AO, uint32_t T, uint32_t d, uint32_t M_pad, uint32_t n_heads, uint32_t n,
+                               uint8_t *q8_scales)
 {
     // n_qt = 8 g + r query tiles: g full groups on the eight-wave kernel; a short remainder (r <= 4) on workgroups of
     // r (rounded up to 1 / 2 / 4) waves, r >= 5 as one more eight-wave group
     const uint32_t n_qt = (T + 31) / 32, r = n_qt % 8, g = r == 0 || r > (uint32_t)ctx->attn_rem ? (n_qt + 7) / 8 : n_qt / 8;
     const uint32_t lds = ATS_STAGES * ATS_SLOT;
-    uint8_t *const no_scales = nullptr;
-    if (q8_scales) {              // "fp8 blocks": e4m3 output + scale bytes
-        if (g) hipLaunchKernelGGL((k_attention_s<8, true>), dim3(n_heads, n, g), dim3(512), lds, ctx->stream, QKV, AO, T, d, M_pad, 0u, q8_scales);
-        if (g * 8 < n_qt) {
-            if (r == 1) hipLaunchKernelGGL((k_attention_s<1, true>), dim3(n_heads, n, 1), dim3(64), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, q8_scales);
-            else if (r == 2) hipLaunchKernelGGL((k_attention_s<2, true>), dim3(n_heads, n, 1), dim3(128), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, q8_scales);
-            else hipLaunchKernelGGL((k_attention_s<4, true>), dim3(n_heads, n, 1), dim3(256), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, q8_scales);
-        }
-        return;
-    }
-    if (g) hipLaunchKernelGGL((k_attention_s<8>), dim3(n_heads, n, g), dim3(512), lds, ctx->stream, QKV, AO, T, d, M_pad, 0u, no_scales);
+    if (g) hipLaunchKernelGGL((k_attention_s<8, Q8>), dim3(n_heads, n, g), dim3(512), lds, ctx->stream, QKV, AO, T, d, M_pad, 0u, q8_scales);
     if (g * 8 < n_qt) {
-        if (r == 1) hipLaunchKernelGGL((k_attention_s<1>), dim3(n_heads, n, 1), dim3(64), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, no_scales);
-        else if (r == 2) hipLaunchKernelGGL((k_attention_s<2>), dim3(n_heads, n, 1), dim3(128), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, no_scales);
-        else hipLaunchKernelGGL((k_attention_s<4>), dim3(n_heads, n, 1), dim3(256), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, no_scales);
+        if (r == 1) hipLaunchKernelGGL((k_attention_s<1, Q8>), dim3(n_heads, n, 1), dim3(64), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, q8_scales);
+        else if (r == 2) hipLaunchKernelGGL((k_attention_s<2, Q8>), dim3(n_heads, n, 1), dim3(128), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, q8_scales);
+        else hipLaunchKernelGGL((k_attention_s<4, Q8>), dim3(n_heads, n, 1), dim3(256), lds, ctx->stream, QKV, AO, T, d, M_pad, g * 8, q8_scales);
     }
+}
+// q8_scales: the "fp8 blocks" form, e4m3 output + scale bytes
+static void launch_attention_vision(d2r_ctx *ctx, const uint16_t *QKV, uint16_t *AO, uint32_t T, uint32_t d, uint32_t M_pad,
+                                    uint32_t n_heads, uint32_t n, uint8_t *q8_scales = nullptr)
+{
+    if (q8_scales) launch_attention_s<true>(ctx, QKV, AO, T, d, M_pad, n_heads, n, q8_scales);
+    else launch_attention_s<false>(ctx, QKV, AO, T, d, M_pad, n_heads, n, nullptr);
 }
 
 // LDS footprint of the resident k_attention (text tower) for a padded sequence length, and the one-time opt-in to
@@ -3100,6 +3116,73 @@ static int attention_setup(d2r_ctx *ctx, uint32_t T_pad, size_t *lds_out)
     return D2R_OK;
 }
 
+// What both towers run their blocks in: the context's workspaces clipws[1..5] for rows_pad rows, and the aux pair of the tile-major
+// bf16 activations ([cols/64][rows_pad][64], see EpiAux): QKV, AO, H and the bf16 residual arrays; only k_layernorm's output (plain
+// blocks) and the patch matrix are row-major
+struct TowerWs {
+    float *X;                     // [1] fp32 residual (the folded loop: lo halves / bytes)
+    uint16_t *Xn, *QKV, *AO, *H;  // [2] operand rows, [3] q / k / v, [4] attention output, [5] fc1 output
+    EpiAux out_tm;                // GEMM whose A is row-major and whose bf16 output is tile-major
+    EpiAux a_tm;                  // GEMM whose A is tile-major (fp32 row-major output)
+};
+static int tower_workspaces(d2r_ctx *ctx, uint32_t rows_pad, uint32_t d, uint32_t mlp, TowerWs *ws)
+{
+    if ((uint64_t)64 * rows_pad >= (1ull << 32)) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "activation plane too large for 32-bit indexing");
+    const size_t bytes[5] = {(size_t)rows_pad * d * 4, (size_t)rows_pad * d * 2, (size_t)rows_pad * 3 * d * 2, (size_t)rows_pad * d * 2, (size_t)rows_pad * mlp * 2};
+    int rc;
+    for (int i = 0; i < 5; i++)
+        if ((rc = d2r_reserve(ctx, ctx->clipws[1 + i], bytes[i]))) return rc;
+    *ws = TowerWs{};
+    ws->X = (float *)ctx->clipws[1].p;
+    ws->Xn = (uint16_t *)ctx->clipws[2].p;
+    ws->QKV = (uint16_t *)ctx->clipws[3].p;
+    ws->AO = (uint16_t *)ctx->clipws[4].p;
+    ws->H = (uint16_t *)ctx->clipws[5].p;
+    ws->out_tm.hm_rows = rows_pad;
+    ws->a_tm.a_rs = 64;
+    ws->a_tm.a_ks = (uint32_t)64 * rows_pad;
+    return D2R_OK;
+}
+
+// The plain block (separate LayerNorm kernels, fp32 residual stream X), in the two pieces the class-token last block cuts it into:
+// k_layernorm -> QKV GEMM, then (after the caller's attention) out-projection + residual -> k_layernorm -> fc1 + GELU -> fc2 + residual
+static int block_qkv(d2r_ctx *ctx, const ClipWeights::Layer &L, const TowerWs &ws, uint32_t rows, uint32_t d)
+{
+    hipLaunchKernelGGL(k_layernorm, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, ws.X, L.ln1_w, L.ln1_b, ws.Xn, rows, d);
+    return launch_gemm<EPI_BIAS_BF16>(ctx, ws.Xn, L.w_qkv, L.b_qkv, ws.QKV, rows, 3 * d, d, ws.out_tm);
+}
+static int block_tail(d2r_ctx *ctx, const ClipWeights::Layer &L, const uint16_t *AO, float *X, uint16_t *Xn, uint16_t *H, uint32_t rows, uint32_t d,
+                      uint32_t mlp, const EpiAux &out_aux, const EpiAux &a_aux)
+{
+    int rc;
+    if ((rc = launch_gemm<EPI_BIAS_RESID_F32>(ctx, AO, L.w_o, L.b_o, X, rows, d, d, a_aux))) return rc;
+    hipLaunchKernelGGL(k_layernorm, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, X, L.ln2_w, L.ln2_b, Xn, rows, d);
+    if ((rc = launch_gemm<EPI_BIAS_GELU_BF16>(ctx, Xn, L.w_fc1, L.b_fc1, H, rows, mlp, d, out_aux))) return rc;
+    return launch_gemm<EPI_BIAS_RESID_F32>(ctx, H, L.w_fc2, L.b_fc2, X, rows, d, mlp, a_aux);
+}
+// `attention`: the tower's launch, QKV -> AO
+template <class Attn>
+static int plain_block(d2r_ctx *ctx, const ClipWeights::Layer &L, const TowerWs &ws, uint32_t rows, uint32_t d, uint32_t mlp, Attn &&attention)
+{
+    int rc;
+    if ((rc = block_qkv(ctx, L, ws, rows, d))) return rc;
+    attention();
+    return block_tail(ctx, L, ws.AO, ws.X, ws.Xn, ws.H, rows, d, mlp, ws.out_tm, ws.a_tm);
+}
+
+// The four residual + statistics epilogues of the folded loop, by ln_fold: 3 = fp32 residual X (+ the bf16 operand copy), 4 = bf16 hi in Xn +
+// lo bytes, 1 = bf16 hi + bf16 lo, 2 = bf16 hi only
+static int launch_resid_stats(d2r_ctx *ctx, int fold, const uint16_t *A, const uint16_t *W, const float *bias, float *X, uint16_t *Xn, uint32_t rows,
+                              uint32_t N, uint32_t K, const EpiAux &st)
+{
+    switch (fold) {
+    case 3: return launch_gemm<EPI_RESID_STATS_F32X>(ctx, A, W, bias, X, rows, N, K, st);
+    case 4: return launch_gemm<EPI_RESID_STATS_SPLIT8>(ctx, A, W, bias, Xn, rows, N, K, st);
+    case 1: return launch_gemm<EPI_RESID_STATS_SPLIT>(ctx, A, W, bias, Xn, rows, N, K, st);
+    default: return launch_gemm<EPI_RESID_STATS_BF16>(ctx, A, W, bias, Xn, rows, N, K, st);
+    }
+}
+
 // The last block on class-token rows only (see k_attention_cls).  QKV must already hold the block's k/v (tile-major) and
 // its q, either there too or for the class tokens only in Qc (compact bf16 [n][d]);
 // the residual stream is X (fp32 row-major) or Xhi (+ Xlo) (bf16 tile-major).  Leaves the block's output rows in
@@ -3109,15 +3192,28 @@ static int last_block_cls(d2r_ctx *ctx, const d2r_clip_desc &D, const ClipWeight
                           const uint16_t *QKV, const uint16_t *Qc, const float *X, const uint16_t *Xhi, const uint16_t *Xlo, float *Xc,
                           uint16_t *AOc, uint16_t *Xnc, uint16_t *Hc, int lo8 = 0)
 {
-    const uint32_t d = D.hidden_size, mlp = D.mlp_size, items = n * D.num_heads;
-    int rc;
+    const uint32_t d = D.hidden_size, items = n * D.num_heads;
     hipLaunchKernelGGL(k_attention_cls, dim3((items + 3) / 4), dim3(256), 0, ctx->stream, QKV, Qc, AOc, T, d, rows_pad, D.num_heads, items);
     hipLaunchKernelGGL(k_gather_cls, dim3((n * d + 255) / 256), dim3(256), 0, ctx->stream, X, Xhi, Xlo, rows_pad, T, d, n, Xc, lo8);
-    if ((rc = launch_gemm<EPI_BIAS_RESID_F32>(ctx, AOc, L.w_o, L.b_o, Xc, n, d, d))) return rc;
-    hipLaunchKernelGGL(k_layernorm, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, Xc, L.ln2_w, L.ln2_b, Xnc, n, d);
-    if ((rc = launch_gemm<EPI_BIAS_GELU_BF16>(ctx, Xnc, L.w_fc1, L.b_fc1, Hc, n, mlp, d))) return rc;
-    if ((rc = launch_gemm<EPI_BIAS_RESID_F32>(ctx, Hc, L.w_fc2, L.b_fc2, Xc, n, d, mlp))) return rc;
-    return D2R_OK;
+    return block_tail(ctx, L, AOc, Xc, Xnc, Hc, n, d, D.mlp_size, EpiAux{}, EpiAux{});
+}
+
+// k_head: post-LayerNorm of one row per item (row pool_row[i] of item i, row 0 without) -> projection -> L2 norm -> embeds, logits.
+// The rows are X (fp32 row-major) or, with Xhi, the bf16 tile-major residual Xhi (+ Xlo; lo8: lo bytes).
+// `n` items of T rows each in arrays of rows_pad rows.
+struct HeadParams {
+    const float *post_w, *post_b, *proj;          // post-LayerNorm, projection [proj_dim][d]
+    uint32_t proj_dim;
+    const float *text;                            // [C][proj_dim] -> logits [n][C] (C = 0: none)
+    uint32_t C;
+    float logit_scale;
+    float *logits, *embeds;
+};
+static void launch_head(d2r_ctx *ctx, const HeadParams &h, uint32_t n, uint32_t rows_pad, uint32_t d, const float *X, uint32_t T,
+                        const uint32_t *pool_row = nullptr, const uint16_t *Xhi = nullptr, const uint16_t *Xlo = nullptr, int lo8 = 0)
+{
+    hipLaunchKernelGGL(k_head, dim3((n + HEAD_NI - 1) / HEAD_NI), dim3(HEAD_THREADS), 0, ctx->stream, X, Xhi, Xlo, rows_pad, pool_row, T, d, h.post_w, h.post_b,
+                       h.proj, h.proj_dim, h.text, h.C, h.logit_scale, h.logits, h.embeds, n, lo8);
 }
 
 // patches (bf16 [n*(T-1) padded to 128][Kp_pad]) -> logits/embeds.  Workspaces:
@@ -3168,7 +3264,7 @@ int d2r_clip_layer0_background(d2r_ctx *ctx, const d2r_clip *clip, const uint16_
 }
 
 // "fp8 blocks": the e4m3 copies of the Linear weights (from the bf16 operand copies: what the bf16 path multiplies with), on first use
-static int ensure_f8_weights(d2r_ctx *ctx, d2r_clip *clip)
+static int ensure_f8_weights(d2r_ctx *ctx, const d2r_clip *clip)
 {
     std::lock_guard<std::mutex> lock(clip->f8_mu);
     if (!clip->f8.empty()) return D2R_OK;
@@ -3176,14 +3272,14 @@ static int ensure_f8_weights(d2r_ctx *ctx, d2r_clip *clip)
     const size_t d = D.hidden_size, mlp = D.mlp_size, nl = D.num_layers;
     const size_t sizes[4] = {3 * d * d, d * d, mlp * d, d * mlp};
     const size_t per_layer = sizes[0] + sizes[1] + sizes[2] + sizes[3];
-    uint8_t *w8 = nullptr;
-    uint32_t *amax = nullptr;
-    if (hipMalloc(&w8, per_layer * nl) != hipSuccess || hipMalloc(&amax, nl * 4 * 4) != hipSuccess) {
-        if (w8) (void)hipFree(w8);
-        return d2r_fail(ctx, D2R_ERR_MEMORY, "hipMalloc failed for the fp8 weight copies");
-    }
-    clip->allocs.push_back(w8);
-    clip->allocs.push_back(amax);
+    // both or neither: a call that fails here leaves nothing in the pool for the next forward to add to
+    D2rDev<uint8_t> copies;
+    int rc;
+    if ((rc = copies.alloc(ctx, per_layer * nl, "the fp8 weight copies"))) return rc;
+    uint32_t *amax = clip->mem.take<uint32_t>(ctx, nl * 4, "the fp8 weight scales");
+    if (!amax) return D2R_ERR_MEMORY;
+    uint8_t *w8 = copies.get();
+    clip->mem.bufs.push_back(std::move(copies));
     D2R_HIP(ctx, hipMemsetAsync(amax, 0, nl * 16, ctx->stream));
     std::vector<d2r_clip::F8Layer> f8(nl);
     for (size_t l = 0; l < nl; l++) {
@@ -3224,15 +3320,13 @@ int d2r_clip_forward(d2r_ctx *ctx, const d2r_clip *clip, const uint16_t *patches
     const uint32_t rows = n * T, rows_pad = round_up(rows, BM);
     const uint32_t prow = n * (T - 1);
     int rc;
+    TowerWs ws;
     if ((rc = d2r_reserve(ctx, ctx->clipws[0], (size_t)round_up(prow, BM) * d * 4))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[1], (size_t)rows_pad * d * 4))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[2], (size_t)rows_pad * d * 2))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[3], (size_t)rows_pad * 3 * d * 2))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[4], (size_t)rows_pad * d * 2))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[5], (size_t)rows_pad * mlp * 2))) return rc;
-    float *patch_out = (float *)ctx->clipws[0].p, *X = (float *)ctx->clipws[1].p;
-    uint16_t *Xn = (uint16_t *)ctx->clipws[2].p, *QKV = (uint16_t *)ctx->clipws[3].p;
-    uint16_t *AO = (uint16_t *)ctx->clipws[4].p, *H = (uint16_t *)ctx->clipws[5].p;
+    if ((rc = tower_workspaces(ctx, rows_pad, d, mlp, &ws))) return rc;
+    float *const patch_out = (float *)ctx->clipws[0].p, *const X = ws.X;
+    uint16_t *const Xn = ws.Xn, *const QKV = ws.QKV, *const AO = ws.AO, *const H = ws.H;
+    const EpiAux &out_tm = ws.out_tm, &a_tm = ws.a_tm;
+    const HeadParams hp{clip->w.post_w, clip->w.post_b, clip->w.proj, D.proj_dim, text_dev, C, logit_scale, logits_dev, embeds_dev};
 
     const int fold = (int)ctx->ln_fold;
     // layer-0 reuse (see k_touch_list): needs the hi + lo-byte residual, square images cut into whole patches, a second layer
@@ -3243,7 +3337,7 @@ int d2r_clip_forward(d2r_ctx *ctx, const d2r_clip *clip, const uint16_t *patches
     const uint32_t cap_pad = round_up(prow, BM);
     if (l0) {
         const PrepCache *pc = nullptr;
-        if ((rc = prep_tables(ctx, (d2r_clip *)clip, reuse->w, reuse->h, 1, &pc))) return rc;
+        if ((rc = prep_tables(ctx, clip, reuse->w, reuse->h, 1, &pc))) return rc;
         if ((rc = d2r_reserve(ctx, ctx->l0_misc, 256 + (size_t)prow * 4 + (size_t)cap_pad * 8))) return rc;
         if ((rc = d2r_reserve(ctx, ctx->l0_a1, (size_t)cap_pad * clip->Kp_pad * 2))) return rc;
         if ((rc = d2r_reserve(ctx, ctx->l0_q2, (size_t)cap_pad * 3 * d * 2))) return rc;
@@ -3266,36 +3360,20 @@ int d2r_clip_forward(d2r_ctx *ctx, const d2r_clip *clip, const uint16_t *patches
         return rc;
     // the last block runs on the class-token rows only (last_block_cls); needs its small workspaces to fit what exists
     const bool cls_last = ctx->cls_last && D.num_layers >= 1 && T <= 1024 && round_up(n, BM) <= round_up(prow, BM);
-    // bf16 activations between kernels are tile-major ([cols/64][rows_pad][64], see EpiAux): QKV, AO, H and the bf16
-    // residual arrays; only k_layernorm's output (fold 0, text tower) and the patch matrix are row-major
-    EpiAux out_tm{}, a_tm{};
-    out_tm.hm_rows = rows_pad;                    // GEMM whose A is row-major and whose bf16 output is tile-major
-    a_tm.a_rs = 64;                               // GEMM whose A is tile-major (fp32 row-major output)
-    a_tm.a_ks = (uint32_t)64 * rows_pad;
-    if ((uint64_t)64 * rows_pad >= (1ull << 32)) return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "activation plane too large for 32-bit indexing");
     if (fold == 0) {
-        // separate LayerNorm kernels, fp32 residual stream (also what the text tower runs)
+        // plain blocks: separate LayerNorm kernels, fp32 residual stream (what the text tower runs)
         hipLaunchKernelGGL(k_embed_ln, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, patch_out, clip->w.cls,
                            clip->w.pos, clip->w.pre_w, clip->w.pre_b, X, rows, T, d, (uint16_t *)nullptr, (float2 *)nullptr, (uint16_t *)nullptr, rows_pad);
         for (uint32_t l = 0; l < D.num_layers; l++) {
             const ClipWeights::Layer &L = clip->layers[l];
-            hipLaunchKernelGGL(k_layernorm, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, X, L.ln1_w, L.ln1_b, Xn,
-                               rows, d);
-            if ((rc = launch_gemm<EPI_BIAS_BF16>(ctx, Xn, L.w_qkv, L.b_qkv, QKV, rows, 3 * d, d, out_tm))) return rc;
             if (cls_last && l + 1 == D.num_layers) {
+                if ((rc = block_qkv(ctx, L, ws, rows, d))) return rc;
                 if ((rc = last_block_cls(ctx, D, L, n, T, rows_pad, QKV, nullptr, X, nullptr, nullptr, patch_out, AO, Xn, H))) return rc;
                 break;
             }
-            launch_attention_vision(ctx, QKV, AO, T, d, rows_pad, D.num_heads, n);
-            if ((rc = launch_gemm<EPI_BIAS_RESID_F32>(ctx, AO, L.w_o, L.b_o, X, rows, d, d, a_tm))) return rc;
-            hipLaunchKernelGGL(k_layernorm, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, X, L.ln2_w, L.ln2_b, Xn,
-                               rows, d);
-            if ((rc = launch_gemm<EPI_BIAS_GELU_BF16>(ctx, Xn, L.w_fc1, L.b_fc1, H, rows, mlp, d, out_tm))) return rc;
-            if ((rc = launch_gemm<EPI_BIAS_RESID_F32>(ctx, H, L.w_fc2, L.b_fc2, X, rows, d, mlp, a_tm))) return rc;
+            if ((rc = plain_block(ctx, L, ws, rows, d, mlp, [&] { launch_attention_vision(ctx, QKV, AO, T, d, rows_pad, D.num_heads, n); }))) return rc;
         }
-        hipLaunchKernelGGL(k_head, dim3((n + HEAD_NI - 1) / HEAD_NI), dim3(HEAD_THREADS), 0, ctx->stream, cls_last ? patch_out : X, (const uint16_t *)nullptr, (const uint16_t *)nullptr, rows_pad,
-                           (const uint32_t *)nullptr, cls_last ? 1u : T, d,
-                           clip->w.post_w, clip->w.post_b, clip->w.proj, D.proj_dim, text_dev, C, logit_scale, logits_dev, embeds_dev, n);
+        launch_head(ctx, hp, n, rows_pad, d, cls_last ? patch_out : X, cls_last ? 1u : T);
         D2R_HIP(ctx, hipGetLastError());
         return D2R_OK;
     }
@@ -3337,7 +3415,7 @@ int d2r_clip_forward(d2r_ctx *ctx, const d2r_clip *clip, const uint16_t *patches
         f8_first = l0 ? 1u : 0u;
         f8_end = cls_last ? D.num_layers - 1 : D.num_layers;
         if (f8_first < f8_end) {
-            if ((rc = ensure_f8_weights(ctx, (d2r_clip *)clip))) return rc;
+            if ((rc = ensure_f8_weights(ctx, clip))) return rc;
             // AO's workspace (2 d bytes per row) holds the attention output's bytes + scales; H's (2 mlp per row) fc1's bytes + scales, then
             // the LayerNorm operand's bytes + scales
             const size_t rp = rows_pad;
@@ -3414,11 +3492,7 @@ int d2r_clip_forward(d2r_ctx *ctx, const d2r_clip *clip, const uint16_t *patches
         launch_attention_vision(ctx, QKV, AO, T, d, rows_pad, D.num_heads, n);
         ctx->timing_end(tk);
         tk = ctx->timing_begin(D2R_T_VIT_OUT);
-        if (xf32) rc = launch_gemm<EPI_RESID_STATS_F32X>(ctx, AO, L.w_o, L.b_o, X, rows, d, d, st);
-        else if (split8) rc = launch_gemm<EPI_RESID_STATS_SPLIT8>(ctx, AO, L.w_o, L.b_o, Xn, rows, d, d, st);
-        else if (split) rc = launch_gemm<EPI_RESID_STATS_SPLIT>(ctx, AO, L.w_o, L.b_o, Xn, rows, d, d, st);
-        else rc = launch_gemm<EPI_RESID_STATS_BF16>(ctx, AO, L.w_o, L.b_o, Xn, rows, d, d, st);
-        if (rc) return rc;
+        if ((rc = launch_resid_stats(ctx, fold, AO, L.w_o, L.b_o, X, Xn, rows, d, d, st))) return rc;
         ctx->timing_end(tk);
         hipLaunchKernelGGL(k_rowstats, dim3((rows_pad + 255) / 256), dim3(256), 0, ctx->stream, part, np, rows_pad, inv_d, AB);
         ln.cs = L.cs_fc1;
@@ -3426,23 +3500,13 @@ int d2r_clip_forward(d2r_ctx *ctx, const d2r_clip *clip, const uint16_t *patches
         if ((rc = launch_gemm<EPI_LN_BIAS_GELU_BF16>(ctx, Xn, L.wf_fc1, L.bf_fc1, H, rows, mlp, d, ln))) return rc;
         ctx->timing_end(tk);
         tk = ctx->timing_begin(D2R_T_VIT_FC2);
-        if (xf32) rc = launch_gemm<EPI_RESID_STATS_F32X>(ctx, H, L.w_fc2, L.b_fc2, X, rows, d, mlp, st);
-        else if (split8) rc = launch_gemm<EPI_RESID_STATS_SPLIT8>(ctx, H, L.w_fc2, L.b_fc2, Xn, rows, d, mlp, st);
-        else if (split) rc = launch_gemm<EPI_RESID_STATS_SPLIT>(ctx, H, L.w_fc2, L.b_fc2, Xn, rows, d, mlp, st);
-        else rc = launch_gemm<EPI_RESID_STATS_BF16>(ctx, H, L.w_fc2, L.b_fc2, Xn, rows, d, mlp, st);
-        if (rc) return rc;
+        if ((rc = launch_resid_stats(ctx, fold, H, L.w_fc2, L.b_fc2, X, Xn, rows, d, mlp, st))) return rc;
         ctx->timing_end(tk);
         if (l + 1 < D.num_layers)
             hipLaunchKernelGGL(k_rowstats, dim3((rows_pad + 255) / 256), dim3(256), 0, ctx->stream, part, np, rows_pad, inv_d, AB);
     }
-    if (cls_last)
-        hipLaunchKernelGGL(k_head, dim3((n + HEAD_NI - 1) / HEAD_NI), dim3(HEAD_THREADS), 0, ctx->stream, patch_out, (const uint16_t *)nullptr, (const uint16_t *)nullptr, rows_pad,
-                           (const uint32_t *)nullptr, 1u, d, clip->w.post_w, clip->w.post_b, clip->w.proj, D.proj_dim, text_dev, C, logit_scale, logits_dev,
-                           embeds_dev, n);
-    else
-    hipLaunchKernelGGL(k_head, dim3((n + HEAD_NI - 1) / HEAD_NI), dim3(HEAD_THREADS), 0, ctx->stream, X, xf32 ? (const uint16_t *)nullptr : (const uint16_t *)Xn,
-                       (const uint16_t *)Xlo, rows_pad, (const uint32_t *)nullptr, T, d, clip->w.post_w, clip->w.post_b, clip->w.proj, D.proj_dim, text_dev, C,
-                       logit_scale, logits_dev, embeds_dev, n, lo8);
+    if (cls_last) launch_head(ctx, hp, n, rows_pad, d, patch_out, 1u);
+    else launch_head(ctx, hp, n, rows_pad, d, X, T, nullptr, xf32 ? nullptr : Xn, Xlo, lo8);
     D2R_HIP(ctx, hipGetLastError());
     return D2R_OK;
 }
@@ -3473,6 +3537,88 @@ size_t d2r_clip_patch_bytes(const d2r_clip *clip, uint32_t n)
 
 // ------------------------------------------------------------ create/destroy
 
+// A tower's weights arrive as one fp32 blob; it is staged on the device whole, then carved in order into fp32 views and bf16 operand copies.
+struct BlobCursor {
+    const float *p;
+    const float *take(size_t n) { const float *q = p; p += n; return q; }
+};
+static int stage_blob(d2r_ctx *ctx, DevPool &mem, const float *weights, size_t n_floats, const char *what, BlobCursor *cur)
+{
+    float *blob = mem.take<float>(ctx, n_floats, what);
+    if (!blob) return D2R_ERR_MEMORY;
+    if (hipMemcpy(blob, weights, n_floats * 4, hipMemcpyHostToDevice) != hipSuccess) return d2r_fail(ctx, D2R_ERR_DEVICE, "weight upload failed");
+    cur->p = blob;
+    return D2R_OK;
+}
+// bf16 operand copy [rows][K_pad] of fp32 [rows][K]
+static int bf16_operand(d2r_ctx *ctx, DevPool &mem, const float *src, uint32_t rows, uint32_t K, uint32_t K_pad, const uint16_t **out)
+{
+    const size_t tot = (size_t)rows * K_pad;
+    uint16_t *p = mem.take<uint16_t>(ctx, tot, "a bf16 weight operand");
+    if (!p) return D2R_ERR_MEMORY;
+    hipLaunchKernelGGL(k_convert_bf16, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, ctx->stream, src, p, rows, K, K_pad);
+    *out = p;
+    return D2R_OK;
+}
+
+// floats of one transformer block in the blob: ln1, q / k / v, out-projection, ln2, fc1, fc2 (weight then bias each)
+static size_t layer_floats(size_t d, size_t mlp) { return 4 * d + 4 * (d * d + d) + mlp * d + mlp + d * mlp + d; }
+
+// One block's weights from the cursor.  q_scale: what the q rows (weight, bias) are multiplied by before the weight is rounded to bf16 once
+// (the vision tower's head_dim^-0.5 * log2(e): k_attention_s / k_attention_cls work in the exp2 domain on scores that need no further scaling;
+// 1 for the text tower).  fold: also the LayerNorm-folded operands of the two Linears that follow a LayerNorm (EPI_LN_*, vision tower).
+static int load_layer(d2r_ctx *ctx, DevPool &mem, BlobCursor &cur, uint32_t d, uint32_t mlp, float q_scale, bool fold, ClipWeights::Layer &L)
+{
+    int rc;
+    L.ln1_w = cur.take(d);
+    L.ln1_b = cur.take(d);
+    // q, k, v are consecutive [d][d] + [d] pairs: fuse into one [3d][d] operand and one [3d] bias
+    const float *const q0 = cur.p;
+    const size_t dd = (size_t)d * d;
+    uint16_t *wqkv = mem.take<uint16_t>(ctx, 3 * dd, "a fused q/k/v operand");
+    float *bqkv = wqkv ? mem.take<float>(ctx, (size_t)3 * d, "a fused q/k/v bias") : nullptr;
+    if (!bqkv) return D2R_ERR_MEMORY;
+    for (int j = 0; j < 3; j++) {
+        const float *wj = cur.take(dd), *bj = cur.take(d);
+        hipLaunchKernelGGL(k_convert_bf16, dim3((uint32_t)((dd + 255) / 256)), dim3(256), 0, ctx->stream, wj, wqkv + j * dd, d, d, d, j == 0 ? q_scale : 1.0f);
+        D2R_HIP(ctx, hipMemcpyAsync(bqkv + (size_t)j * d, bj, (size_t)d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        if (j == 0 && q_scale != 1.0f) hipLaunchKernelGGL(k_scale_f32, dim3((d + 255) / 256), dim3(256), 0, ctx->stream, bqkv, d, q_scale);
+    }
+    L.w_qkv = wqkv;
+    L.b_qkv = bqkv;
+    uint16_t *wf1 = nullptr;
+    float *cs1 = nullptr, *bf1 = nullptr;
+    if (fold) {
+        uint16_t *wfq = mem.take<uint16_t>(ctx, 3 * dd, "a folded q/k/v operand");
+        float *csq = wfq ? mem.take<float>(ctx, (size_t)3 * d, "folded q/k/v column sums") : nullptr;
+        float *bfq = csq ? mem.take<float>(ctx, (size_t)3 * d, "a folded q/k/v bias") : nullptr;
+        wf1 = bfq ? mem.take<uint16_t>(ctx, (size_t)mlp * d, "a folded fc1 operand") : nullptr;
+        cs1 = wf1 ? mem.take<float>(ctx, mlp, "folded fc1 column sums") : nullptr;
+        bf1 = cs1 ? mem.take<float>(ctx, mlp, "a folded fc1 bias") : nullptr;
+        if (!bf1) return D2R_ERR_MEMORY;
+        for (int j = 0; j < 3; j++) {             // layer_norm1 into q / k / v
+            const float *wj = q0 + (size_t)j * (dd + d), *bj = wj + dd;
+            hipLaunchKernelGGL(k_fold_ln_weight, dim3((d + 3) / 4), dim3(256), 0, ctx->stream, wj, L.ln1_w, L.ln1_b, bj, wfq + j * dd, csq + (size_t)j * d,
+                               bfq + (size_t)j * d, d, d, j == 0 ? q_scale : 1.0f);
+        }
+        L.wf_qkv = wfq; L.cs_qkv = csq; L.bf_qkv = bfq;
+    }
+    if ((rc = bf16_operand(ctx, mem, cur.take(dd), d, d, d, &L.w_o))) return rc;
+    L.b_o = cur.take(d);
+    L.ln2_w = cur.take(d);
+    L.ln2_b = cur.take(d);
+    const float *w1 = cur.take((size_t)mlp * d);
+    if ((rc = bf16_operand(ctx, mem, w1, mlp, d, d, &L.w_fc1))) return rc;
+    L.b_fc1 = cur.take(mlp);
+    if (fold) {                                   // layer_norm2 into fc1
+        hipLaunchKernelGGL(k_fold_ln_weight, dim3((mlp + 3) / 4), dim3(256), 0, ctx->stream, w1, L.ln2_w, L.ln2_b, L.b_fc1, wf1, cs1, bf1, mlp, d);
+        L.wf_fc1 = wf1; L.cs_fc1 = cs1; L.bf_fc1 = bf1;
+    }
+    if ((rc = bf16_operand(ctx, mem, cur.take((size_t)d * mlp), d, mlp, mlp, &L.w_fc2))) return rc;
+    L.b_fc2 = cur.take(d);
+    return D2R_OK;
+}
+
 extern "C" int d2r_clip_create(d2r_ctx *ctx, const d2r_clip_desc *desc, const float *weights, size_t n_floats,
                                d2r_clip **out)
 {
@@ -3481,106 +3627,32 @@ extern "C" int d2r_clip_create(d2r_ctx *ctx, const d2r_clip_desc *desc, const fl
     if (d % 128 || mlp % 128 || d > 1024 || desc->proj_dim > 1024 || d / desc->num_heads != 64 || S % P)
         return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "unsupported CLIP geometry (need head_dim 64, d,mlp % 128 == 0, d <= 1024)");
     D2R_HIP(ctx, hipSetDevice(ctx->device));
-    d2r_clip *c = new d2r_clip();
+    std::unique_ptr<d2r_clip> c(new d2r_clip());          // every early return frees what was allocated so far
     c->ctx = ctx;
     c->desc = *desc;
     c->T = (S / P) * (S / P) + 1;
     c->Kp = 3 * P * P;
     c->Kp_pad = round_up(c->Kp, BK);
     const uint32_t T = c->T, Dp = desc->proj_dim;
-    size_t expect = (size_t)d * c->Kp + d + (size_t)T * d + 2 * d +
-                    (size_t)desc->num_layers * (4 * (size_t)d + 4 * ((size_t)d * d + d) + (size_t)mlp * d + mlp + (size_t)d * mlp + d) +
-                    2 * d + (size_t)Dp * d;
-    if (n_floats != expect) {
-        delete c;
-        return d2r_fail(ctx, D2R_ERR_INVALID, "weight blob size does not match the descriptor");
-    }
-    // stage the whole blob on the device once, then carve fp32 views and bf16 copies
-    float *blob = nullptr;
-    if (hipMalloc(&blob, n_floats * 4) != hipSuccess) {
-        delete c;
-        return d2r_fail(ctx, D2R_ERR_MEMORY, "hipMalloc failed for CLIP weights");
-    }
-    c->allocs.push_back(blob);
-    if (hipMemcpy(blob, weights, n_floats * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        d2r_clip_destroy(c);
-        return d2r_fail(ctx, D2R_ERR_DEVICE, "weight upload failed");
-    }
-    size_t off = 0;
-    auto f32 = [&](size_t n) { const float *p = blob + off; off += n; return p; };
-    bool ok = true;
-    auto bf16 = [&](const float *src, uint32_t rows, uint32_t K, uint32_t K_pad) -> const uint16_t * {
-        uint16_t *p = nullptr;
-        if (hipMalloc(&p, (size_t)rows * K_pad * 2) != hipSuccess) { ok = false; return nullptr; }
-        c->allocs.push_back(p);
-        size_t tot = (size_t)rows * K_pad;
-        hipLaunchKernelGGL(k_convert_bf16, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, ctx->stream, src, p, rows, K, K_pad);
-        return p;
-    };
-    c->w.w_patch = bf16(f32((size_t)d * c->Kp), d, c->Kp, c->Kp_pad);
-    c->w.cls = f32(d);
-    c->w.pos = f32((size_t)T * d);
-    c->w.pre_w = f32(d);
-    c->w.pre_b = f32(d);
+    const size_t expect = (size_t)d * c->Kp + d + (size_t)T * d + 2 * d + desc->num_layers * layer_floats(d, mlp) + 2 * d + (size_t)Dp * d;
+    if (n_floats != expect) return d2r_fail(ctx, D2R_ERR_INVALID, "weight blob size does not match the descriptor");
+    BlobCursor cur{};
+    int rc;
+    if ((rc = stage_blob(ctx, c->mem, weights, n_floats, "CLIP weights", &cur))) return rc;
+    if ((rc = bf16_operand(ctx, c->mem, cur.take((size_t)d * c->Kp), d, c->Kp, c->Kp_pad, &c->w.w_patch))) return rc;
+    c->w.cls = cur.take(d);
+    c->w.pos = cur.take((size_t)T * d);
+    c->w.pre_w = cur.take(d);
+    c->w.pre_b = cur.take(d);
     c->layers.resize(desc->num_layers);
-    for (uint32_t l = 0; l < desc->num_layers && ok; l++) {
-        ClipWeights::Layer &L = c->layers[l];
-        L.ln1_w = f32(d);
-        L.ln1_b = f32(d);
-        // q, k, v are consecutive [d][d] + [d] pairs: fuse into one [3d][d] operand and one [3d] bias
-        uint16_t *wqkv = nullptr;
-        float *bqkv = nullptr;
-        if (hipMalloc(&wqkv, (size_t)3 * d * d * 2) != hipSuccess || hipMalloc(&bqkv, (size_t)3 * d * 4) != hipSuccess) { ok = false; break; }
-        c->allocs.push_back(wqkv);
-        c->allocs.push_back(bqkv);
-        // the q rows (weights, bias) carry the attention scale head_dim^-0.5 * log2(e): k_attention_s / k_attention_cls work in the exp2
-        // domain on scores that need no further scaling (the scaled weight is rounded to bf16 once, like the unscaled one was)
-        for (int j = 0; j < 3; j++) {
-            const float *wj = f32((size_t)d * d), *bj = f32(d);
-            size_t tot = (size_t)d * d;
-            hipLaunchKernelGGL(k_convert_bf16, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, ctx->stream, wj,
-                               wqkv + (size_t)j * d * d, d, d, d, j == 0 ? ATTN_Q_SCALE : 1.0f);
-            hipMemcpyAsync(bqkv + (size_t)j * d, bj, (size_t)d * 4, hipMemcpyDeviceToDevice, ctx->stream);
-            if (j == 0) hipLaunchKernelGGL(k_scale_f32, dim3((d + 255) / 256), dim3(256), 0, ctx->stream, bqkv, d, ATTN_Q_SCALE);
-        }
-        L.w_qkv = wqkv;
-        L.b_qkv = bqkv;
-        // layer_norm1 folded into q/k/v (EPI_LN_BIAS_BF16): the three [d][d] + [d] pairs sit 3 blocks back in the blob
-        uint16_t *wfq = nullptr, *wf1 = nullptr;
-        float *csq = nullptr, *bfq = nullptr, *cs1 = nullptr, *bf1 = nullptr;
-        if (hipMalloc(&wfq, (size_t)3 * d * d * 2) != hipSuccess || hipMalloc(&csq, (size_t)3 * d * 4) != hipSuccess ||
-            hipMalloc(&bfq, (size_t)3 * d * 4) != hipSuccess || hipMalloc(&wf1, (size_t)mlp * d * 2) != hipSuccess ||
-            hipMalloc(&cs1, (size_t)mlp * 4) != hipSuccess || hipMalloc(&bf1, (size_t)mlp * 4) != hipSuccess) { ok = false; break; }
-        for (void *pp : {(void *)wfq, (void *)csq, (void *)bfq, (void *)wf1, (void *)cs1, (void *)bf1}) c->allocs.push_back(pp);
-        {
-            const float *q0 = blob + off - 3 * ((size_t)d * d + d);
-            for (int j = 0; j < 3; j++) {
-                const float *wj = q0 + (size_t)j * ((size_t)d * d + d), *bj = wj + (size_t)d * d;
-                hipLaunchKernelGGL(k_fold_ln_weight, dim3((d + 3) / 4), dim3(256), 0, ctx->stream, wj, L.ln1_w, L.ln1_b, bj,
-                                   wfq + (size_t)j * d * d, csq + (size_t)j * d, bfq + (size_t)j * d, d, d, j == 0 ? ATTN_Q_SCALE : 1.0f);
-            }
-        }
-        L.wf_qkv = wfq; L.cs_qkv = csq; L.bf_qkv = bfq;
-        L.w_o = bf16(f32((size_t)d * d), d, d, d);
-        L.b_o = f32(d);
-        L.ln2_w = f32(d);
-        L.ln2_b = f32(d);
-        const float *w1 = f32((size_t)mlp * d);
-        L.w_fc1 = bf16(w1, mlp, d, d);
-        L.b_fc1 = f32(mlp);
-        hipLaunchKernelGGL(k_fold_ln_weight, dim3((mlp + 3) / 4), dim3(256), 0, ctx->stream, w1, L.ln2_w, L.ln2_b, L.b_fc1, wf1, cs1, bf1, mlp, d);
-        L.wf_fc1 = wf1; L.cs_fc1 = cs1; L.bf_fc1 = bf1;
-        L.w_fc2 = bf16(f32((size_t)d * mlp), d, mlp, mlp);
-        L.b_fc2 = f32(d);
-    }
-    c->w.post_w = f32(d);
-    c->w.post_b = f32(d);
-    c->w.proj = f32((size_t)Dp * d);
-    if (!ok || hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        d2r_clip_destroy(c);
+    for (ClipWeights::Layer &L : c->layers)
+        if ((rc = load_layer(ctx, c->mem, cur, d, mlp, ATTN_Q_SCALE, true, L))) return rc;
+    c->w.post_w = cur.take(d);
+    c->w.post_b = cur.take(d);
+    c->w.proj = cur.take((size_t)Dp * d);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)
         return d2r_fail(ctx, D2R_ERR_DEVICE, "CLIP weight conversion failed");
-    }
-    *out = c;
+    *out = c.release();
     return D2R_OK;
 }
 
@@ -3589,7 +3661,6 @@ extern "C" void d2r_clip_destroy(d2r_clip *c)
     if (!c) return;
     if (c->ctx && c->ctx->bg_patches_for == (const void *)c) c->ctx->bg_patches_for = nullptr;   // a later model may reuse the address
     if (c->ctx && c->ctx->bg_l0_for == (const void *)c) c->ctx->bg_l0_for = nullptr;
-    for (void *p : c->allocs) hipFree(p);
     delete c;
 }
 
@@ -3598,7 +3669,7 @@ extern "C" void d2r_clip_destroy(d2r_clip *c)
 struct d2r_text {
     d2r_ctx *ctx;
     d2r_text_desc desc;
-    std::vector<void *> allocs;
+    DevPool mem;
     const float *tok, *pos, *fin_w, *fin_b, *proj;
     std::vector<ClipWeights::Layer> layers;
 };
@@ -3611,75 +3682,29 @@ extern "C" int d2r_text_create(d2r_ctx *ctx, const d2r_text_desc *desc, const fl
     if (d % 128 || mlp % 128 || d > 1024 || desc->proj_dim > 1024 || d / desc->num_heads != 64 || Tc == 0 || Tc > 512)
         return d2r_fail(ctx, D2R_ERR_UNSUPPORTED, "unsupported text tower geometry (need head_dim 64, d,mlp % 128 == 0)");
     (void)hipSetDevice(ctx->device);
-    size_t expect = (size_t)V * d + (size_t)Tc * d +
-                    (size_t)desc->num_layers * (4 * (size_t)d + 4 * ((size_t)d * d + d) + (size_t)mlp * d + mlp + (size_t)d * mlp + d) +
-                    2 * d + (size_t)desc->proj_dim * d;
+    const size_t expect = (size_t)V * d + (size_t)Tc * d + desc->num_layers * layer_floats(d, mlp) + 2 * d + (size_t)desc->proj_dim * d;
     if (n_floats != expect) return d2r_fail(ctx, D2R_ERR_INVALID, "text weight blob size does not match the descriptor");
-    d2r_text *t = new d2r_text();
+    std::unique_ptr<d2r_text> t(new d2r_text());
     t->ctx = ctx;
     t->desc = *desc;
-    float *blob = nullptr;
-    if (hipMalloc(&blob, n_floats * 4) != hipSuccess) { delete t; return d2r_fail(ctx, D2R_ERR_MEMORY, "hipMalloc failed for text weights"); }
-    t->allocs.push_back(blob);
-    if (hipMemcpy(blob, weights, n_floats * 4, hipMemcpyHostToDevice) != hipSuccess) { d2r_text_destroy(t); return d2r_fail(ctx, D2R_ERR_DEVICE, "weight upload failed"); }
-    size_t off = 0;
-    auto f32 = [&](size_t n) { const float *p = blob + off; off += n; return p; };
-    bool ok = true;
-    auto bf16 = [&](const float *src, uint32_t rows, uint32_t K) -> uint16_t * {
-        uint16_t *p = nullptr;
-        if (hipMalloc(&p, (size_t)rows * K * 2) != hipSuccess) { ok = false; return nullptr; }
-        t->allocs.push_back(p);
-        size_t tot = (size_t)rows * K;
-        hipLaunchKernelGGL(k_convert_bf16, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, ctx->stream, src, p, rows, K, K);
-        return p;
-    };
-    t->tok = f32((size_t)V * d);
-    t->pos = f32((size_t)Tc * d);
+    BlobCursor cur{};
+    int rc;
+    if ((rc = stage_blob(ctx, t->mem, weights, n_floats, "text weights", &cur))) return rc;
+    t->tok = cur.take((size_t)V * d);
+    t->pos = cur.take((size_t)Tc * d);
     t->layers.resize(desc->num_layers);
-    for (uint32_t l = 0; l < desc->num_layers && ok; l++) {
-        ClipWeights::Layer &L = t->layers[l];
-        L.ln1_w = f32(d);
-        L.ln1_b = f32(d);
-        uint16_t *wqkv = nullptr;
-        float *bqkv = nullptr;
-        if (hipMalloc(&wqkv, (size_t)3 * d * d * 2) != hipSuccess || hipMalloc(&bqkv, (size_t)3 * d * 4) != hipSuccess) { ok = false; break; }
-        t->allocs.push_back(wqkv);
-        t->allocs.push_back(bqkv);
-        for (int j = 0; j < 3; j++) {
-            const float *wj = f32((size_t)d * d), *bj = f32(d);
-            size_t tot = (size_t)d * d;
-            hipLaunchKernelGGL(k_convert_bf16, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, ctx->stream, wj,
-                               wqkv + (size_t)j * d * d, d, d, d);
-            (void)hipMemcpyAsync(bqkv + (size_t)j * d, bj, (size_t)d * 4, hipMemcpyDeviceToDevice, ctx->stream);
-        }
-        L.w_qkv = wqkv;
-        L.b_qkv = bqkv;
-        L.w_o = bf16(f32((size_t)d * d), d, d);
-        L.b_o = f32(d);
-        L.ln2_w = f32(d);
-        L.ln2_b = f32(d);
-        L.w_fc1 = bf16(f32((size_t)mlp * d), mlp, d);
-        L.b_fc1 = f32(mlp);
-        L.w_fc2 = bf16(f32((size_t)d * mlp), d, mlp);
-        L.b_fc2 = f32(d);
-    }
-    t->fin_w = f32(d);
-    t->fin_b = f32(d);
-    t->proj = f32((size_t)desc->proj_dim * d);
-    if (!ok || hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        d2r_text_destroy(t);
+    for (ClipWeights::Layer &L : t->layers)
+        if ((rc = load_layer(ctx, t->mem, cur, d, mlp, 1.0f, false, L))) return rc;
+    t->fin_w = cur.take(d);
+    t->fin_b = cur.take(d);
+    t->proj = cur.take((size_t)desc->proj_dim * d);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)
         return d2r_fail(ctx, D2R_ERR_DEVICE, "text weight conversion failed");
-    }
-    *out = t;
+    *out = t.release();
     return D2R_OK;
 }
 
-extern "C" void d2r_text_destroy(d2r_text *t)
-{
-    if (!t) return;
-    for (void *p : t->allocs) (void)hipFree(p);
-    delete t;
-}
+extern "C" void d2r_text_destroy(d2r_text *t) { delete t; }
 
 // CLIPModel text forward (causal pre-LN transformer, EOS pooling, text_projection, L2 norm):
 // replaces the text half of reference clip_scoring.py:177-180, run ONCE per task instead of per batch.
@@ -3692,42 +3717,26 @@ extern "C" int d2r_text_encode(d2r_ctx *ctx, const d2r_text *tt, const int32_t *
     (void)hipSetDevice(ctx->device);
     const uint32_t d = D.hidden_size, mlp = D.mlp_size, rows = Cn * T, rows_pad = round_up(rows, BM);
     int rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[1], (size_t)rows_pad * d * 4))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[2], (size_t)rows_pad * d * 2))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[3], (size_t)rows_pad * 3 * d * 2))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[4], (size_t)rows_pad * d * 2))) return rc;
-    if ((rc = d2r_reserve(ctx, ctx->clipws[5], (size_t)rows_pad * mlp * 2))) return rc;
+    TowerWs ws;
+    if ((rc = tower_workspaces(ctx, rows_pad, d, mlp, &ws))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->pix, (size_t)rows * 4 + (size_t)Cn * 4))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->logits, (size_t)Cn * D.proj_dim * 4))) return rc;
     if ((rc = d2r_reserve(ctx, ctx->text, 16))) return rc;
-    float *X = (float *)ctx->clipws[1].p;
-    uint16_t *Xn = (uint16_t *)ctx->clipws[2].p, *QKV = (uint16_t *)ctx->clipws[3].p;
-    uint16_t *AO = (uint16_t *)ctx->clipws[4].p, *H = (uint16_t *)ctx->clipws[5].p;
     int32_t *ids_dev = (int32_t *)ctx->pix.p;
     uint32_t *pool = (uint32_t *)(ids_dev + rows);
     D2R_HIP(ctx, hipMemcpyAsync(ids_dev, input_ids, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_text_embed, dim3(rows), dim3(128), 0, ctx->stream, ids_dev, tt->tok, tt->pos, X, pool, Cn, T, d,
+    hipLaunchKernelGGL(k_text_embed, dim3(rows), dim3(128), 0, ctx->stream, ids_dev, tt->tok, tt->pos, ws.X, pool, Cn, T, d,
                        D.vocab_size);
     const uint32_t T_pad = round_up(T, 32);
     size_t attn_lds = 0;
     if ((rc = attention_setup(ctx, T_pad, &attn_lds))) return rc;
-    EpiAux out_tm{}, a_tm{};                      // tile-major bf16 activations, as in the vision tower
-    out_tm.hm_rows = rows_pad;
-    a_tm.a_rs = 64;
-    a_tm.a_ks = (uint32_t)64 * rows_pad;
-    for (uint32_t l = 0; l < D.num_layers; l++) {
-        const ClipWeights::Layer &L = tt->layers[l];
-        hipLaunchKernelGGL(k_layernorm, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, X, L.ln1_w, L.ln1_b, Xn, rows, d);
-        if ((rc = launch_gemm<EPI_BIAS_BF16>(ctx, Xn, L.w_qkv, L.b_qkv, QKV, rows, 3 * d, d, out_tm))) return rc;
-        hipLaunchKernelGGL(k_attention<true>, dim3(D.num_heads, Cn), dim3(ATTN_THREADS), attn_lds, ctx->stream, QKV, AO, T, T_pad, d, rows_pad);
-        if ((rc = launch_gemm<EPI_BIAS_RESID_F32>(ctx, AO, L.w_o, L.b_o, X, rows, d, d, a_tm))) return rc;
-        hipLaunchKernelGGL(k_layernorm, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, X, L.ln2_w, L.ln2_b, Xn, rows, d);
-        if ((rc = launch_gemm<EPI_BIAS_GELU_BF16>(ctx, Xn, L.w_fc1, L.b_fc1, H, rows, mlp, d, out_tm))) return rc;
-        if ((rc = launch_gemm<EPI_BIAS_RESID_F32>(ctx, H, L.w_fc2, L.b_fc2, X, rows, d, mlp, a_tm))) return rc;
-    }
-    hipLaunchKernelGGL(k_head, dim3((Cn + HEAD_NI - 1) / HEAD_NI), dim3(HEAD_THREADS), 0, ctx->stream, X, (const uint16_t *)nullptr, (const uint16_t *)nullptr, rows_pad, (const uint32_t *)pool, T, d, tt->fin_w,
-                       tt->fin_b, tt->proj, D.proj_dim, (const float *)ctx->text.p, 0u, 1.0f, (float *)nullptr,
-                       (float *)ctx->logits.p, Cn);
+    for (const ClipWeights::Layer &L : tt->layers)
+        if ((rc = plain_block(ctx, L, ws, rows, d, mlp, [&] {
+                hipLaunchKernelGGL(k_attention<true>, dim3(D.num_heads, Cn), dim3(ATTN_THREADS), attn_lds, ctx->stream, ws.QKV, ws.AO, T, T_pad, d, rows_pad);
+            })))
+            return rc;
+    const HeadParams hp{tt->fin_w, tt->fin_b, tt->proj, D.proj_dim, (const float *)ctx->text.p, 0u, 1.0f, nullptr, (float *)ctx->logits.p};      // embeddings only
+    launch_head(ctx, hp, Cn, rows_pad, d, ws.X, T, pool);
     D2R_HIP(ctx, hipGetLastError());
     D2R_HIP(ctx, hipMemcpyAsync(embeds_out, ctx->logits.p, (size_t)Cn * D.proj_dim * 4, hipMemcpyDeviceToHost, ctx->stream));
     D2R_HIP(ctx, hipStreamSynchronize(ctx->stream));
